@@ -13,6 +13,18 @@ independent CSR count of SURVEY.md §8d rides along as csr_equivalent_gbs.
     python bench.py [--gpus N] [--steps K] [--warmup W] [--n 256] [--kind 27]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one part per GPU)
     ... --strong    256³ nodes in total split over the N parts (config 3)
+
+The K timed steps rotate over independently built copies of A, at most 32
+and at most one per step (identical copies differ in rate with where their
+pages land), so ms_per_step and value, the wall clock of the
+K steps / K, average over the placements of config.operator_copies_rotated
+copies.
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--dump-outputs DIR writes the y of the last timed step (DIR/y_part<p>.npy).
+--full adds everything that takes runs of its own: the per-phase attribution,
+the int32-column variant, the box's HBM probe, the halo leg (halo_1gpu), the
+rocprofv3 PMC traffic, the one-process leg of N > 1 and the CPU baselines.
 """
 from __future__ import annotations
 
@@ -108,6 +120,8 @@ def cpu_baseline_mpi(kind, dims, shape, seconds=12.0):
 
 
 PROBE_BYTES = 1 << 30
+PLACEMENT_COPIES = 32      # operator copies the timed steps rotate over at most (main)
+PLACEMENT_BYTES = 128.0e9  # ... as far as their format bytes fit this much HBM per GPU
 
 
 def rccl_run_info(infos, world):
@@ -545,6 +559,29 @@ def cg_mode(args, pamd, backend, parts, A, ngpu, use_dist, sync):
     return line
 
 
+DUMP_BYTES = 48 << 20  # --dump-outputs: all parts' files together (under 64 MB with their headers)
+
+
+def dump_outputs(dirname, parts, rows, y, nparts_all):
+    """--dump-outputs DIR: the owned values of y after the last timed step, one
+    file DIR/y_part<p>.npy per part (each rank writes its own parts'), float32
+    or float64 (complex values as (n, 2) re/im pairs).  A part with more than
+    its share of DUMP_BYTES is written as a fixed sample: the sorted owned
+    positions drawn by a generator seeded with the part id alone, so two
+    builds of the library write the same entries."""
+    os.makedirs(dirname, exist_ok=True)
+    host = y.to_host()
+    for p in parts.part_ids:
+        own = rows.partition.local(p).oid_to_lid - 1
+        v = np.ascontiguousarray(host.local(p)[own])
+        keep = DUMP_BYTES // nparts_all // v.dtype.itemsize
+        if len(v) > keep:
+            v = v[np.sort(np.random.default_rng(20250114 + p).choice(len(v), keep, replace=False))]
+        if np.iscomplexobj(v):
+            v = v.view(v.real.dtype).reshape(-1, 2)
+        np.save(os.path.join(dirname, f"y_part{p}.npy"), v)
+
+
 def launch_ranks(n):
     """Run this script under torch.distributed.run with n ranks (one part and
     one GPU per rank, HIPDistributedBackend) as a child process; rank 0
@@ -569,25 +606,34 @@ def main():
                     help="strong scaling (BASELINE config 3): --n^3 nodes in total, split over the parts")
     ap.add_argument("--kind", type=int, default=27, choices=[7, 27])
     ap.add_argument("--dtype", default="f64", choices=list(DTYPES))
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: per-phase attribution, int32 columns, HBM "
+                         "probe, halo leg, PMC traffic, one-process leg, CPU baselines (the --no-* options "
+                         "drop single legs of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps write the y of the last one as DIR/y_part<p>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 HBM-traffic passes")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: skip the rocprofv3 HBM-traffic passes")
     ap.add_argument("--no-halo-leg", action="store_true",
-                    help="skip the halo_1gpu object (config 3 on (2,2,2) parts of the one GPU)")
+                    help="with --full: skip the halo_1gpu object (config 3 on (2,2,2) parts of the one GPU)")
     ap.add_argument("--child-pmc", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--child-halo", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--child-oneproc", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--oneproc-devices", default="",
                     help="devices of the one-process leg's parts (default 0..N-1; e.g. 0,0 rehearses it on one GPU)")
     ap.add_argument("--no-oneproc", action="store_true",
-                    help="skip the one-process leg of N > 1 runs (all N parts driven by one process)")
-    ap.add_argument("--cg", type=int, default=0, help="time K CG iterations instead (own JSON line)")
+                    help="with --full: skip the one-process leg of N > 1 runs (all N parts driven by one process)")
+    ap.add_argument("--cg", type=int, default=0, help="time K CG iterations instead (own JSON line; --full "
+                                                      "adds nothing to it, --dump-outputs is refused)")
     ap.add_argument("--tune", default="", help="process-default knobs before anything is built (A/B runs): "
                                                  "key=v[,key=v]")
     ap.add_argument("--distributed", action="store_true",
                     help="one part per process (HIPDistributedBackend, RCCL) even for one process: "
                          "rehearses the torchrun path of --gpus N > 1 on a single GPU")
     args = ap.parse_args()
+    if args.cg > 0 and args.dump_outputs:
+        ap.error("--dump-outputs writes the y of the timed mul! steps: not with --cg")
     if args.child_pmc or args.child_oneproc:
         import pamd
         for kv in filter(None, args.tune.split(",")):
@@ -688,14 +734,39 @@ def main():
     # Small problems fit the 256 MB MALL (SURVEY.md §7 hard part iv): rotate
     # through copies of (A, x, y) so every step streams from HBM.
     per_gpu = B_local / max(1, len(parts.part_ids))
-    ncopies = 1 if per_gpu >= 1.0e9 else int(np.ceil(1.0e9 / per_gpu))
+    ncache = 1 if per_gpu >= 1.0e9 else int(np.ceil(1.0e9 / per_gpu))
+    # The rate of one operator copy depends on where its pages land (DESIGN.md
+    # §4.1, §8 item 5: identical copies of the headline run 0.54-0.65 ms, the
+    # same kernel), so a line that times one copy repeats that draw, not the
+    # kernel.  The timed steps rotate over copies of A built independently:
+    # at most PLACEMENT_COPIES, at most one per timed step (every copy built
+    # is timed, K // ncopies or one more step each), all alive within
+    # PLACEMENT_BYTES per GPU; a copy that no longer fits the device ends the
+    # building and the run goes on with those it has.  x and y stay the same
+    # vectors, as with one copy, and each extra copy runs once, untimed, when
+    # it is built.  ms_per_step, still the wall clock of the K steps / K, is
+    # the mean over the copies' draws: the same expectation as one copy's, a
+    # fraction of its spread (profiles/r07/a/).
+    ncopies = max(ncache, min(PLACEMENT_COPIES, int(PLACEMENT_BYTES // per_gpu), args.steps))
     sets = [(A, x, y)]
     for k in range(1, ncopies):
-        Ak = pamd.drivers.stencil_operator(parts, N, args.kind, dtype, partition=partition)
-        xk = pamd.PVector.from_host(pamd.map_parts(
-            lambda s: np.random.default_rng(20250114 + s.part).uniform(-1, 1, s.num_lids).astype(dtype),
-            cols.partition), Ak.cols)
-        sets.append((Ak, xk, pamd.PVector.undef(Ak.rows, dtype)))
+        try:
+            Ak = pamd.drivers.stencil_operator(parts, N, args.kind, dtype, partition=partition)
+        except pamd.PAError:
+            if k < ncache:
+                raise  # the copies that keep the operator out of the cache are not optional
+            if len(sets) > ncache:
+                sets.pop()  # room for the vectors and legs that follow
+            break
+        if k < ncache:
+            xk = pamd.PVector.from_host(pamd.map_parts(
+                lambda s: np.random.default_rng(20250114 + s.part).uniform(-1, 1, s.num_lids).astype(dtype),
+                cols.partition), Ak.cols)
+            sets.append((Ak, xk, pamd.PVector.undef(Ak.rows, dtype)))
+        else:
+            sets.append((Ak,) + sets[k % ncache][1:])
+            pamd.mul_(sets[k][2], Ak, sets[k][1])
+    ncopies = len(sets)
     sync()
 
     for i in range(args.warmup):
@@ -723,6 +794,8 @@ def main():
         elapsed = float(t.item())
     ms_per_step = 1e3 * elapsed / args.steps
     value = B_all / (elapsed / args.steps) / 1e9
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, parts, rows, yi, int(np.prod(shape)))
     rccl = None
     if use_dist:
         # bytes this process posted to RCCL (ncclSend / ncclRecv of the halo
@@ -754,16 +827,19 @@ def main():
         for c in ctxs:
             c.set_timing(True)
         for i in range(reps):
-            Ai, xi, yi = sets[i % ncopies]
+            Ai, xi, yi = sets[i % ncache]
             pamd.mul_(yi, Ai, xi)
         sync()
         return {p: c.kernel_times() for p, c in zip(parts.part_ids, ctxs)}
-    phases = phase_times()
-    per_part = {p: {k: round(v, 4) if isinstance(v, float) else v for k, v in t.items()} for p, t in phases.items()}
-    if use_dist:
-        allp = [None] * world
-        dist.all_gather_object(allp, per_part)
-        per_part = {k: v for d in allp for k, v in d.items()}
+    per_part = None
+    if args.full:
+        phases = phase_times()
+        per_part = {p: {k: round(v, 4) if isinstance(v, float) else v for k, v in t.items()}
+                    for p, t in phases.items()}
+        if use_dist:
+            allp = [None] * world
+            dist.all_gather_object(allp, per_part)
+            per_part = {k: v for d in allp for k, v in d.items()}
     p0 = parts.part_ids[0]
     info, s_nhids, n_snd0, n_rcv0 = infos[p0]
     # the dominant kernels' device time per step: the HIP-event span of the
@@ -774,40 +850,44 @@ def main():
     kernel_ms = span_ms
     spmv_bytes = B_local if grouped_here else format_bytes(info, s_nhids, n_snd0, n_rcv0, S)
     achieved = spmv_bytes / (kernel_ms * 1e-3) / 1e9
-    # the same kernels with int32 column ids everywhere (spmv_format=0 on
-    # this run's contexts), for reference
-    for c in ctxs:
-        c.tune("spmv_format", 0)
-    sync()
-    c0.span_start()
-    for i in range(reps):
-        Ai, xi, yi = sets[i % ncopies]
-        pamd.mul_(yi, Ai, xi)
-    c0.span_stop()
-    kernel_ms_int32 = c0.span_ms() / reps
-    bytes_int32 = 0
-    for p in (parts.part_ids if grouped_here else [p0]):
-        inf, nh, ns_, nr_ = infos[p]
-        bytes_int32 += format_bytes(dict(inf, **A.values.local(p).traffic()), nh, ns_, nr_, S)
-    for c in ctxs:
-        c.tune("spmv_format", None)
+    int32_columns = {}
+    if args.full:
+        # the same kernels with int32 column ids everywhere (spmv_format=0 on
+        # this run's contexts), for reference
+        for c in ctxs:
+            c.tune("spmv_format", 0)
+        sync()
+        c0.span_start()
+        for i in range(reps):
+            Ai, xi, yi = sets[i % ncache]
+            pamd.mul_(yi, Ai, xi)
+        c0.span_stop()
+        kernel_ms_int32 = c0.span_ms() / reps
+        bytes_int32 = 0
+        for p in (parts.part_ids if grouped_here else [p0]):
+            inf, nh, ns_, nr_ = infos[p]
+            bytes_int32 += format_bytes(dict(inf, **A.values.local(p).traffic()), nh, ns_, nr_, S)
+        for c in ctxs:
+            c.tune("spmv_format", None)
+        int32_columns = {"int32_columns_kernel_ms": round(kernel_ms_int32, 4),
+                         "int32_columns_achieved": round(bytes_int32 / (kernel_ms_int32 * 1e-3) / 1e9, 1)}
     # the probe reads as many bytes per launch as the timed loop cycles
-    # through (ncopies operator copies when one would fit the 256 MB
+    # through (ncache operator copies when one would fit the 256 MB
     # Infinity Cache), so that neither side is served from it
-    box = box_hbm_gbs(pamd, spmv_bytes * ncopies) if world == 1 and ngpu == 1 else None
+    box = box_hbm_gbs(pamd, spmv_bytes * ncache) if args.full and world == 1 and ngpu == 1 else None
     # ... and one launch of the operator's own size, rotating over 2 GiB (a
     # short SpMV pays one launch's ramp-up and drain per step; C2's 149 MB)
     box_launch = None
-    if box is not None:
+    if args.full and box is not None:
         try:
             box_launch = pamd._lib.hbm_probe_launch(0, int(spmv_bytes), max(2 << 30, 8 * int(spmv_bytes)), 40)
         except pamd._lib.PAError:
             box_launch = None
     halo_leg = None
-    if world == 1 and ngpu == 1 and not args.strong and not args.no_halo_leg:
+    if args.full and world == 1 and ngpu == 1 and not args.strong and not args.no_halo_leg:
         halo_leg = halo_1gpu(args, pamd, dtype, S)
-    traffic, tnote = (None, {"note": "skipped (--no-pmc)"})
-    if rank == 0 and ngpu == 1 and not args.no_pmc:
+    traffic, tnote = (None, {"note": "skipped (--no-pmc)" if args.full else "not measured (--full measures it)"})
+    if args.full and rank == 0 and ngpu == 1 and not args.no_pmc:
         traffic, tnote = pmc_traffic(args)
         if traffic is None:
             tnote = {"note": tnote}
@@ -902,8 +982,7 @@ def main():
             "column_format": (f"pattern slices {info['pattern_slices']}/{info['nslices']}, "
                               f"delta16 slices {info.get('delta16_slices', 0)}, "
                               f"regular rows {info['regular_rows']}/{info['nrows']}, side rows {info['side_rows']}"),
-            "int32_columns_kernel_ms": round(kernel_ms_int32, 4),
-            "int32_columns_achieved": round(bytes_int32 / (kernel_ms_int32 * 1e-3) / 1e9, 1),
+            **int32_columns,
             "box_read_gbs": None if box is None else round(box[0], 1),
             "box_copy_gbs": None if box is None else round(box[1], 1),
             "achieved_vs_box_read": None if box is None else round(achieved / box[0], 4),
@@ -920,12 +999,12 @@ def main():
     # N ranks: the same problem with all N parts in ONE process (the Julia
     # binding's model), measured by a child of rank 0 while the other ranks
     # wait (their GPUs idle)
-    if use_dist and not args.no_oneproc and (ngpu > 1 or args.oneproc_devices):
+    if args.full and use_dist and not args.no_oneproc and (ngpu > 1 or args.oneproc_devices):
         barrier()
         if rank == 0:
             line["one_process"] = one_process_leg(args)
         barrier()
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         if ngpu == 1:
             line["cpu_baseline"] = cpu_baseline(args.kind, args.n, args.cpu_seconds)
             if halo_leg is not None:

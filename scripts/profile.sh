@@ -4,8 +4,8 @@
 # off under the profiler (--no-pmc).
 set -o pipefail
 OUT=${1:-gpurun_out/prof}
-ARGS=${2:-"--steps 20 --warmup 3 --no-cpu-baseline --no-pmc"}
-SHORT="--steps 5 --warmup 1 --no-cpu-baseline --no-pmc"
+ARGS=${2:-"--full --steps 20 --warmup 3 --no-cpu-baseline --no-pmc"}
+SHORT="--full --steps 5 --warmup 1 --no-cpu-baseline --no-pmc"
 mkdir -p $OUT
 export TMPDIR=/tmp
 timeout -k 10 240 rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt --output-format csv -- python3 bench.py $ARGS > $OUT/kt.log 2>&1 || exit 1

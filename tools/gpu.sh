@@ -15,13 +15,13 @@
 #   pmcpy:CTR[,CTR..]:script args  rocprofv3 --kernel-trace --pmc CTR.. of python3 script args
 #   py:script args        python script args              > OUT/py<i>.log
 #   cmd:program args      a host program (no GPU), e.g. the C port   > OUT/cmd<i>.log
-# Profiled runs default to "--steps 10 --warmup 2 --no-cpu-baseline --no-pmc".
+# Profiled runs default to "--full --steps 10 --warmup 2 --no-cpu-baseline --no-pmc".
 set -o pipefail
 OUT=$1
 shift
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-PROF_ARGS="--steps 10 --warmup 2 --no-cpu-baseline --no-pmc"
+PROF_ARGS="--full --steps 10 --warmup 2 --no-cpu-baseline --no-pmc"
 i=0
 for step in "$@"; do
   i=$((i + 1))
