@@ -31,10 +31,8 @@ static thread_local std::string g_err;
 void set_error(const std::string& msg) { g_err = msg; }
 
 // kernels (pa_spmv.hip, pa_kernels.hip)
-void launch_spmv_part(int which, int64_t nwork, const int32_t* list, const pa_mat* A, const void* x,
-                      void* y, const int32_t* ymap, bool has_alpha, int bmode, const void* alpha,
-                      const void* beta, void* dotp, hipStream_t st,
-                      const SpmvPart* cgp = nullptr);
+void launch_spmv_part(SliceKind kind, const SpmvPart& q, bool has_alpha, int bmode, const void* alpha,
+                      const void* beta, hipStream_t st);
 void launch_delta16(pa_mat* A, int64_t noids, const int32_t* kind, int32_t* ok, hipStream_t st);
 void launch_pattern_detect(pa_mat* A, int64_t noids, int min_pct, int32_t* kind, int32_t* plen, int32_t* pat,
                            uint64_t* mask, int32_t* pghost, int32_t* nirreg, hipStream_t st);
@@ -126,10 +124,10 @@ void launch_pull(int dtype, int64_t n, const int32_t* lids, const pa_combine_pla
                  const int64_t* elem, const void* const* bases, void* v, hipStream_t st, hipEvent_t ev = nullptr);
 void launch_fill(int dtype, int64_t n, int64_t base, const int32_t* map, void* v, const void* s,
                  hipStream_t st);
-int launch_spmv_merged(int n, const int* which, const SpmvPart* parts, bool has_alpha, int bmode,
+int launch_spmv_merged(int n, const SliceKind* kinds, const SpmvPart* parts, bool has_alpha, int bmode,
                        const void* alpha, const void* beta, pa_ctx* owner,
                        hipStream_t st);
-void launch_spmv_group(int which, int np, const SpmvPart* parts, bool has_alpha, int bmode, const void* alpha,
+void launch_spmv_group(SliceKind kind, int np, const SpmvPart* parts, bool has_alpha, int bmode, const void* alpha,
                        const void* beta, hipStream_t st);
 void launch_pack_group(int dtype, const PackGroup& g, hipStream_t st);
 void launch_pull_group(int dtype, const PullGroup& g, hipStream_t st);
@@ -3199,7 +3197,7 @@ int pa_mat_traffic(const pa_mat* A, int64_t* value_bytes, int64_t* index_bytes, 
   CHECK_ARG(A, "null matrix");
   TuneScope ts(A->ctx);
   const int64_t S = (int64_t)dtype_size(A->dtype), H = A->H, W = H / 64;
-  const bool pat = knobs().spmv_format == 1 && A->has_pat;
+  const bool pat = pattern_layout(A);
   const bool split = A->d_bnd_list != nullptr;
   int64_t v = 0, ix = 0, m = 0;
   for (int64_t s = 0; s < A->nslices; ++s) {
@@ -3276,6 +3274,105 @@ static void cg_ghosts(const CGFuse* fz, int i, const pa_mat* A, const pa_vec* r,
   launch_cg_ghost(A->dtype, A->nrows, r->n, r->d, fz->u_old[i], fz->u_new[i], fz->xacc[i], fz->st[i], st);
 }
 
+// The slices of a matrix that one phase of a mul! launches: the interior
+// slices (no ghost column: before the halo), the boundary slices and side
+// rows (after it), or all of them (no halo in flight).
+enum SlicePhase { kInterior, kBoundary, kWhole };
+struct SliceWork {
+  SliceKind kind;
+  int64_t nwork;
+  const int32_t* list;  // slice ids (null: 0..nwork-1)
+};
+struct SliceList {
+  SliceWork w[8];
+  int n = 0;
+  void add(SliceKind kind, int64_t nwork, const int32_t* list) { w[n++] = SliceWork{kind, nwork, list}; }
+  const SliceWork* begin() const { return w; }
+  const SliceWork* end() const { return w + n; }
+};
+
+// Empty entries are listed too; a kind's interior entry precedes its
+// boundary entry.  The callers launch the entries in orders of their own.
+static SliceList slice_list(const pa_mat* A, SlicePhase phase) {
+  SliceList L;
+  const bool in = phase != kBoundary, bnd = phase != kInterior;
+  if (pattern_layout(A)) {
+    if (in) {
+      L.add(kPattern, A->np_int, A->d_pint_list);
+      L.add(kInt32, A->nx_int, A->d_xint_list);
+      L.add(kDelta16, A->nd_int, A->d_dint_list);
+    }
+    if (bnd) {
+      L.add(kPattern, A->np_bnd, A->d_pbnd_list);
+      L.add(kInt32, A->nx_bnd, A->d_xbnd_list);
+      L.add(kDelta16, A->nd_bnd, A->d_dbnd_list);
+      L.add(kSide, A->s_nslices, nullptr);
+    }
+    // the triple SELL: a whole call runs its slices in their own order, without the lists
+    if (phase == kWhole) L.add(kTriple, A->t_nslices, nullptr);
+    else if (in) L.add(kTriple, A->nt_int, A->d_t_int_list);
+    else L.add(kTriple, A->nt_bnd, A->d_t_bnd_list);
+  } else if (A->d_bnd_list) {  // split layout (the interior list may be empty)
+    if (in) L.add(kInt32, A->nslices_int, A->d_int_list);
+    if (bnd) L.add(kInt32, A->nslices - A->nslices_int, A->d_bnd_list);
+  } else if (in) {
+    L.add(kInt32, A->nslices, nullptr);
+  }
+  return L;
+}
+
+// One mul!(c, A, b, α, β) over the n local parts, its arguments checked:
+// what every launch path of the call reads.
+struct SpmvCall {
+  int n;
+  pa_mat* const* A;
+  pa_vec* const* y;
+  const pa_index* const* y_idx;
+  pa_vec* const* x;
+  pa_xchg* const* xg;
+  bool any_x;  // the call exchanges the ghosts of x (every xg[i] set)
+  int dt;
+  bool has_alpha;
+  int bmode;
+  const void* alpha;
+  const void* beta;
+  std::vector<void*> dotp;  // per part: the partials of the fused dot (null: no dot)
+  bool want_dot;
+  CGState* const* dot_tail;        // the fold of the dot ends in the device CG's α (one part per process)
+  std::vector<hipEvent_t*> tslot;  // per part: the four timing events of this call (null: not timed)
+  const CGFuse* fz;
+
+  const int32_t* ymap(int i) const { return y_idx[i]->own_contig ? nullptr : y_idx[i]->d_oid_to_lid; }
+
+  SpmvPart part(int i, int64_t nwork, const int32_t* list) const {
+    SpmvPart q{nwork, list, A[i], x[i]->d, y[i]->d, ymap(i), dotp[i]};
+    if (fz) {
+      q.xu = fz->u_old[i];
+      q.un = fz->u_new[i];
+      q.xacc = fz->xacc[i];
+      q.cg = fz->st[i];
+    }
+    return q;
+  }
+
+  // The end of part i, after its slices and the halo: the ghosts of the fused
+  // CG update, the long rows (they may read ghost columns) and the fold of
+  // the dot partials (main, side and triple slices, long rows, in order).
+  void finish_part(int i, hipStream_t st) const {
+    const pa_mat* M = A[i];
+    pa_ctx* c = M->ctx;
+    cg_ghosts(fz, i, M, x[i], st);
+    const int64_t long_base = long_dot_base(M);
+    launch_spmv_long(M, x[i]->d, y[i]->d, ymap(i), has_alpha, bmode, alpha, beta, dotp[i], long_base, st);
+    if (!want_dot) return;
+    const int nbp = (int)(long_base + M->n_long);
+    if (dot_tail)
+      launch_fold_cg_alpha(dt, nbp, M->d_dotp, c->d_fold, c->d_result, c->d_ticket, dot_tail[i], st);
+    else
+      launch_fold(dt == PA_C64 || dt == PA_C128, nbp, M->d_dotp, c->d_fold, c->d_result, c->d_ticket, st);
+  }
+};
+
 // The grouped path applies when every part of the call shares one stream
 // pair (pa_ctx_create_shared: same device, one in-order chain) and every
 // halo neighbour is a part of this call served by the pull-unpack.
@@ -3316,11 +3413,15 @@ static int group_ok(int n, pa_mat* const A[], pa_xchg* const xg[], bool any_x, i
 // launch per slice kind and phase for all parts (kernel-argument tables),
 // instead of the same sequence per part.  Every slice is computed by the
 // same wave code as in the per-part launches: results are identical.
-static int spmv_grouped(int n, pa_mat* const A[], pa_vec* const y[], const pa_index* const y_idx[],
-                        pa_vec* const x[], pa_xchg* const xg[], bool any_x, bool has_alpha, int bmode,
-                        const void* alpha, const void* beta, const std::vector<void*>& dotp, bool want_dot,
-                        CGState* const* dot_tail, const std::vector<hipEvent_t*>& tslot, int dt, bool direct,
-                        const CGFuse* fz) {
+static int spmv_grouped(const SpmvCall& C, bool direct) {
+  const int n = C.n;
+  pa_mat* const* A = C.A;
+  pa_vec* const* x = C.x;
+  pa_xchg* const* xg = C.xg;
+  const bool any_x = C.any_x;
+  const int dt = C.dt;
+  const CGFuse* fz = C.fz;
+  const std::vector<hipEvent_t*>& tslot = C.tslot;
   pa_ctx* c0 = A[0]->ctx;
   HIPC(hipSetDevice(c0->device));
   const hipStream_t sm = c0->s_main, sc = c0->s_comm;
@@ -3391,25 +3492,23 @@ static int spmv_grouped(int n, pa_mat* const A[], pa_vec* const y[], const pa_in
     HIPC(hipEventRecord(c0->ev_recvd, sc));
   }
   HIPC(hipGetLastError());
-  std::vector<SpmvPart> P0, P1, P4, P5;
-  auto part = [&](int i, int64_t nwork, const int32_t* list) {
-    const int32_t* ymap = y_idx[i]->own_contig ? nullptr : y_idx[i]->d_oid_to_lid;
-    SpmvPart q{nwork, list, A[i], x[i]->d, y[i]->d, ymap, dotp[i]};
-    if (fz) {
-      q.xu = fz->u_old[i];
-      q.un = fz->u_new[i];
-      q.xacc = fz->xacc[i];
-      q.cg = fz->st[i];
-    }
-    return q;
-  };
-  auto launch_all = [&](int which, const std::vector<SpmvPart>& v, hipStream_t st = nullptr) {
-    if (!v.empty()) launch_spmv_group(which, (int)v.size(), v.data(), has_alpha, bmode, alpha, beta, st ? st : sm);
+  // every part's slices of one kind and phase as one launch; side_tail: the
+  // parts' side rows as trailing entries of the (pattern) launch
+  auto launch_kind = [&](SlicePhase phase, SliceKind kind, bool side_tail) {
+    std::vector<SpmvPart> v;
+    for (int i = 0; i < n; ++i)
+      for (const SliceWork& w : slice_list(A[i], phase))
+        if (w.kind == kind) v.push_back(C.part(i, w.nwork, w.list));
+    if (side_tail)
+      for (int i = 0; i < n; ++i)
+        if (A[i]->s_nslices > 0) {
+          SpmvPart q = C.part(i, A[i]->s_nslices, nullptr);
+          q.side = true;
+          v.push_back(q);
+        }
+    if (!v.empty()) launch_spmv_group(kind, (int)v.size(), v.data(), C.has_alpha, C.bmode, C.alpha, C.beta, sm);
   };
   if (dmark ? mark(2) : mark(0)) return -1;
-  // no halo in flight (none, or pulled already on this stream): every slice
-  // kind of every part in one launch — side rows and int32 slices first, so
-  // their few long waves start early, then delta16, multi-pattern, pattern
   int merged = 1;
   bool big_part = false;  // one part alone fills the GPU many times: per-kind launches (knobs().spmv_merge_max)
   if (knobs().spmv_merge_max > 0 && n == 1) big_part = A[0]->nslices > knobs().spmv_merge_max;
@@ -3422,131 +3521,61 @@ static int spmv_grouped(int n, pa_mat* const A[], pa_vec* const y[], const pa_in
   bool tail_only = knobs().side_tail && !any_x && !fz && 2 * n <= PA_GROUP_MAX && A[0]->R <= 2;
   for (int i = 0; i < n && tail_only; ++i) {
     const pa_mat* M = A[i];
-    tail_only = knobs().spmv_format == 1 && M->has_pat && M->np_bnd == 0 && M->nx_int + M->nx_bnd == 0 &&
+    tail_only = pattern_layout(M) && M->np_bnd == 0 && M->nx_int + M->nx_bnd == 0 &&
                 M->nd_int + M->nd_bnd == 0 && M->t_nslices == 0 && M->n_long == 0 &&
                 (M->s_nslices == 0 || M->maxlen_side <= 8);
   }
   if (knobs().spmv_merge && !big_part && !tail_only && (!any_x || direct)) {
-    std::vector<SpmvPart> E;
-    std::vector<int> W;
-    auto add = [&](int which, int i, int64_t nwork, const int32_t* list) {
-      if (nwork <= 0) return;
-      E.push_back(part(i, nwork, list));
-      W.push_back(which);
-    };
+    // no halo in flight (none, or pulled already on this stream): every slice
+    // kind of every part in one launch.  The table's order is also its cache
+    // key and decides which waves land where: each row's kinds for every
+    // part, then the next row — side rows and int32 slices first, so their
+    // few long waves start early, then delta16 and triple SELL, then pattern
     // (side rows first also when they are short: FD7's Dirichlet rows last
     // made C2 0.7 % slower, 0.0285 -> 0.0287 ms, profiles/r05/o/)
-    for (int i = 0; i < n; ++i)
-      if (knobs().spmv_format == 1 && A[i]->has_pat) add(2, i, A[i]->s_nslices, nullptr);
-    for (int i = 0; i < n; ++i) {
-      if (knobs().spmv_format == 1 && A[i]->has_pat) {
-        add(1, i, A[i]->nx_int, A[i]->d_xint_list);
-        add(1, i, A[i]->nx_bnd, A[i]->d_xbnd_list);
-      } else if (A[i]->d_bnd_list) {
-        add(1, i, A[i]->nslices_int, A[i]->d_int_list);
-        add(1, i, A[i]->nslices - A[i]->nslices_int, A[i]->d_bnd_list);
-      } else {
-        add(1, i, A[i]->nslices, nullptr);
-      }
-    }
-    for (int i = 0; i < n; ++i)
-      if (knobs().spmv_format == 1 && A[i]->has_pat) {
-        add(4, i, A[i]->nd_int, A[i]->d_dint_list);
-        add(4, i, A[i]->nd_bnd, A[i]->d_dbnd_list);
-        add(5, i, A[i]->t_nslices, nullptr);
-      }
-    for (int i = 0; i < n; ++i)
-      if (knobs().spmv_format == 1 && A[i]->has_pat) {
-        add(0, i, A[i]->np_int, A[i]->d_pint_list);
-        add(0, i, A[i]->np_bnd, A[i]->d_pbnd_list);
-      }
-    merged = launch_spmv_merged((int)E.size(), W.data(), E.data(), has_alpha, bmode, alpha, beta, c0,
-                                sm);
+    constexpr struct {
+      SliceKind kind[2];
+      int nkinds;
+    } kMergedOrder[] = {{{kSide}, 1}, {{kInt32}, 1}, {{kDelta16, kTriple}, 2}, {{kPattern}, 1}};
+    std::vector<SpmvPart> E;
+    std::vector<SliceKind> W;
+    for (const auto& row : kMergedOrder)
+      for (int i = 0; i < n; ++i)
+        for (int k = 0; k < row.nkinds; ++k)
+          for (const SliceWork& w : slice_list(A[i], kWhole))
+            if (w.kind == row.kind[k] && w.nwork > 0) {
+              E.push_back(C.part(i, w.nwork, w.list));
+              W.push_back(w.kind);
+            }
+    merged = launch_spmv_merged((int)E.size(), W.data(), E.data(), C.has_alpha, C.bmode, C.alpha, C.beta, c0, sm);
     if (merged < 0) PA_FAIL("mul!: merged launch table (device allocation or copy) failed");
     if (merged == 0 && !dmark && (mark(1) || mark(2))) return -1;
   }
-  if (merged) {
-  // interior slices (no ghost column): overlap with the pulls on the comm stream
-  for (int i = 0; i < n; ++i) {
-    if (knobs().spmv_format == 1 && A[i]->has_pat) {
-      P0.push_back(part(i, A[i]->np_int, A[i]->d_pint_list));
-      P1.push_back(part(i, A[i]->nx_int, A[i]->d_xint_list));
-      P4.push_back(part(i, A[i]->nd_int, A[i]->d_dint_list));
-      P5.push_back(part(i, A[i]->nt_int, A[i]->d_t_int_list));
-    } else if (A[i]->d_bnd_list) {
-      P1.push_back(part(i, A[i]->nslices_int, A[i]->d_int_list));
-    } else {
-      P1.push_back(part(i, A[i]->nslices, nullptr));
-    }
-  }
-  // the side rows as the pattern launch's trailing waves (spmv_side_tail):
-  // no halo in flight, the side rows short, pattern and side entries within
-  // one group launch, no fused CG update
-  bool side_tailed = false;
-  if (knobs().side_tail && (!any_x || direct) && !fz && 2 * n <= PA_GROUP_MAX) {
-    bool ok = false;
-    for (int i = 0; i < n; ++i) {
-      const bool pat = knobs().spmv_format == 1 && A[i]->has_pat;
-      if (!pat) { ok = false; break; }
-      if (A[i]->s_nslices > 0) {
-        if (A[i]->maxlen_side > 8) { ok = false; break; }
-        ok = true;
+  if (merged) {  // one launch per slice kind and phase
+    // the side rows as the pattern launch's trailing waves (spmv_side_tail):
+    // no halo in flight, the side rows short, pattern and side entries within
+    // one group launch, no fused CG update
+    bool side_tailed = false;
+    if (knobs().side_tail && (!any_x || direct) && !fz && 2 * n <= PA_GROUP_MAX) {
+      for (int i = 0; i < n; ++i) {
+        if (!pattern_layout(A[i])) { side_tailed = false; break; }
+        if (A[i]->s_nslices > 0) {
+          if (A[i]->maxlen_side > 8) { side_tailed = false; break; }
+          side_tailed = true;
+        }
       }
     }
-    if (ok) {
-      std::vector<SpmvPart> PT = P0;
-      for (int i = 0; i < n; ++i)
-        if (A[i]->s_nslices > 0) {
-          SpmvPart q = part(i, A[i]->s_nslices, nullptr);
-          q.side = true;
-          PT.push_back(q);
-        }
-      launch_all(6, PT);
-      side_tailed = true;
-    }
+    // interior slices (no ghost column): overlap with the pulls on the comm stream
+    constexpr SliceKind kInteriorOrder[] = {kPattern, kTriple, kDelta16, kInt32};
+    for (SliceKind k : kInteriorOrder) launch_kind(kInterior, k, k == kPattern && side_tailed);
+    if (!dmark && mark(1)) return -1;
+    if (any_x && !direct) HIPC(hipStreamWaitEvent(sm, c0->ev_recvd, 0));
+    if (!dmark && mark(2)) return -1;
+    constexpr SliceKind kBoundaryOrder[] = {kPattern, kTriple, kDelta16, kInt32, kSide};
+    for (SliceKind k : kBoundaryOrder)
+      if (!(k == kSide && side_tailed)) launch_kind(kBoundary, k, false);
   }
-  if (!side_tailed) launch_all(0, P0);
-  launch_all(5, P5);
-  launch_all(4, P4);
-  launch_all(1, P1);
-  if (!dmark && mark(1)) return -1;
-  if (any_x && !direct) HIPC(hipStreamWaitEvent(sm, c0->ev_recvd, 0));
-  if (!dmark && mark(2)) return -1;
-  P0.clear(); P1.clear(); P4.clear(); P5.clear();
-  std::vector<SpmvPart> P2;
-  for (int i = 0; i < n; ++i) {
-    if (knobs().spmv_format == 1 && A[i]->has_pat) {
-      P0.push_back(part(i, A[i]->np_bnd, A[i]->d_pbnd_list));
-      P4.push_back(part(i, A[i]->nd_bnd, A[i]->d_dbnd_list));
-      P5.push_back(part(i, A[i]->nt_bnd, A[i]->d_t_bnd_list));
-      P1.push_back(part(i, A[i]->nx_bnd, A[i]->d_xbnd_list));
-      if (!side_tailed) P2.push_back(part(i, A[i]->s_nslices, nullptr));
-    } else if (A[i]->d_bnd_list) {
-      P1.push_back(part(i, A[i]->nslices - A[i]->nslices_int, A[i]->d_bnd_list));
-    }
-  }
-  launch_all(0, P0);
-  launch_all(5, P5);
-  launch_all(4, P4);
-  launch_all(1, P1);
-  launch_all(2, P2);
-  }  // per-kind launches
-  for (int i = 0; i < n; ++i) {
-    const int32_t* ymap = y_idx[i]->own_contig ? nullptr : y_idx[i]->d_oid_to_lid;
-    const bool pat = knobs().spmv_format == 1 && A[i]->has_pat;
-    const int64_t long_base = A[i]->nslices + (pat ? A[i]->s_nslices + A[i]->t_nslices : 0);
-    cg_ghosts(fz, i, A[i], x[i], sm);
-    launch_spmv_long(A[i], x[i]->d, y[i]->d, ymap, has_alpha, bmode, alpha, beta, dotp[i], long_base, sm);
-    if (want_dot) {
-      pa_ctx* c = A[i]->ctx;
-      const bool cplx = dt == PA_C64 || dt == PA_C128;
-      const int nbp = (int)(long_base + A[i]->n_long);
-      if (dot_tail)
-        launch_fold_cg_alpha(dt, nbp, A[i]->d_dotp, c->d_fold, c->d_result, c->d_ticket, dot_tail[i], sm);
-      else
-        launch_fold(cplx, nbp, A[i]->d_dotp, c->d_fold, c->d_result, c->d_ticket, sm);
-    }
-  }
+  for (int i = 0; i < n; ++i) C.finish_part(i, sm);
   if (mark(3)) return -1;
   HIPC(hipGetLastError());
   for (int i = 0; i < n; ++i)
@@ -3554,54 +3583,28 @@ static int spmv_grouped(int n, pa_mat* const A[], pa_vec* const y[], const pa_in
   return 0;
 }
 
-// One phase of one part's slices (0: interior, before the halo; 1: boundary
-// slices and side rows, after it): one merged launch (pa_tune spmv_merge)
-// or one launch per slice kind.
-static int launch_phase(int phase, pa_mat* A, const void* x, void* y, const int32_t* ymap, bool has_alpha,
-                        int bmode, const void* alpha, const void* beta, void* dotp, hipStream_t st,
-                        const CGFuse* fz = nullptr, int fi = 0) {
+// One phase of part i's slices on stream st (kInterior: before the halo;
+// kBoundary: the slices reading ghosts and the side rows, after it): one
+// merged launch (pa_tune spmv_merge) or one launch per slice kind.
+static int launch_phase(const SpmvCall& C, SlicePhase phase, int i, hipStream_t st) {
+  const pa_mat* A = C.A[i];
+  constexpr SliceKind kPhaseOrder[] = {kSide, kInt32, kDelta16, kTriple, kPattern};
   std::vector<SpmvPart> E;
-  std::vector<int> W;
-  auto add = [&](int which, int64_t nwork, const int32_t* list) {
-    if (nwork <= 0) return;
-    SpmvPart q{nwork, list, A, x, y, ymap, dotp};
-    if (fz) {
-      q.xu = fz->u_old[fi];
-      q.un = fz->u_new[fi];
-      q.xacc = fz->xacc[fi];
-      q.cg = fz->st[fi];
-    }
-    E.push_back(q);
-    W.push_back(which);
-  };
-  if (knobs().spmv_format == 1 && A->has_pat) {
-    if (phase == 0) {
-      add(1, A->nx_int, A->d_xint_list);
-      add(4, A->nd_int, A->d_dint_list);
-      add(5, A->nt_int, A->d_t_int_list);
-      add(0, A->np_int, A->d_pint_list);
-    } else {
-      add(2, A->s_nslices, nullptr);
-      add(1, A->nx_bnd, A->d_xbnd_list);
-      add(4, A->nd_bnd, A->d_dbnd_list);
-      add(5, A->nt_bnd, A->d_t_bnd_list);
-      add(0, A->np_bnd, A->d_pbnd_list);
-    }
-  } else if (A->d_bnd_list) {  // split layout (the interior list may be empty)
-    if (phase == 0) add(1, A->nslices_int, A->d_int_list);
-    else add(1, A->nslices - A->nslices_int, A->d_bnd_list);
-  } else if (phase == 0) {
-    add(1, A->nslices, nullptr);
-  }
+  std::vector<SliceKind> W;
+  for (SliceKind k : kPhaseOrder)
+    for (const SliceWork& w : slice_list(A, phase))
+      if (w.kind == k && w.nwork > 0) {
+        E.push_back(C.part(i, w.nwork, w.list));
+        W.push_back(k);
+      }
   if (E.empty()) return 0;
   if (E.size() > 1 && knobs().spmv_merge && !(knobs().spmv_merge_max > 0 && A->nslices > knobs().spmv_merge_max)) {
-    const int rc = launch_spmv_merged((int)E.size(), W.data(), E.data(), has_alpha, bmode, alpha, beta, A->ctx,
-                                      st);
+    const int rc = launch_spmv_merged((int)E.size(), W.data(), E.data(), C.has_alpha, C.bmode, C.alpha, C.beta,
+                                      A->ctx, st);
     if (rc < 0) PA_FAIL("mul!: merged launch table (device allocation or copy) failed");
     if (rc == 0) return 0;
   }
-  for (size_t k = 0; k < E.size(); ++k)
-    launch_spmv_part(W[k], E[k].nwork, E[k].list, A, x, y, ymap, has_alpha, bmode, alpha, beta, dotp, st, &E[k]);
+  for (size_t k = 0; k < E.size(); ++k) launch_spmv_part(W[k], E[k], C.has_alpha, C.bmode, C.alpha, C.beta, st);
   return 0;
 }
 
@@ -3627,9 +3630,12 @@ static int launch_phase(int phase, pa_mat* A, const void* x, void* y, const int3
 // (pa_xchg::fast_key / fast_seq); any other use of the send buffers
 // (pre_pack_wait_part, the grouped path) restarts the chain with the waits.
 // About 8 HIP calls per part and call instead of ≈24.
-static int spmv_barrier_issue(int n, pa_vec* const x[], pa_xchg* const xg[], int dt, const TransportPlan& T,
-                              bool threads, const std::function<int(int)>& interior,
-                              const std::function<int(int)>& boundary, bool pull_on_main) {
+static int spmv_barrier_issue(const SpmvCall& C, const TransportPlan& T, bool threads,
+                              const std::function<int(int)>& interior, const std::function<int(int)>& boundary,
+                              bool pull_on_main) {
+  const int n = C.n, dt = C.dt;
+  pa_vec* const* x = C.x;
+  pa_xchg* const* xg = C.xg;
   uint64_t key = 1469598103934665603ull ^ (uint64_t)n;
   for (int i = 0; i < n; ++i) key = (key ^ xg[i]->id) * 1099511628211ull;
   bool chain = true;
@@ -3716,7 +3722,7 @@ static int spmv_impl(int n, pa_mat* const A[], pa_vec* const y[], const pa_index
         // one partial per main, side and triple-SELL slice and long row;
         // zeroed once: the slices a call does not launch (moved to the
         // triple SELL) add 0 to the fold
-        const int64_t nbp = std::max<int64_t>(A[i]->nslices + A[i]->s_nslices + A[i]->t_nslices + A[i]->n_long, 1);
+        const int64_t nbp = std::max<int64_t>(dot_base(A[i], kTriple) + A[i]->t_nslices + A[i]->n_long, 1);
         HIPC(hipMalloc(&A[i]->d_dotp, nbp * 16));
         HIPC(hipMemset(A[i]->d_dotp, 0, nbp * 16));
       }
@@ -3764,10 +3770,9 @@ static int spmv_impl(int n, pa_mat* const A[], pa_vec* const y[], const pa_index
     }
     tslot[i] = &c->tev[4 * c->tn];
   }
-  if (grouped) {
-    return spmv_grouped(n, A, y, y_idx, x, xg, any_x, has_alpha, bmode, alpha, beta, dotp, want_dot, dot_tail,
-                        tslot, dt, gmode == 2, fz);
-  }
+  const SpmvCall C{n, A, y, y_idx, x, xg, any_x, dt, has_alpha, bmode, alpha, beta, std::move(dotp), want_dot,
+                   dot_tail, std::move(tslot), fz};
+  if (grouped) return spmv_grouped(C, gmode == 2);
 
   auto pack = [&](int i) -> int {
     pa_ctx* c = xg[i]->ctx;
@@ -3779,11 +3784,10 @@ static int spmv_impl(int n, pa_mat* const A[], pa_vec* const y[], const pa_index
   auto interior = [&](int i) -> int {
     pa_ctx* c = A[i]->ctx;
     HIPC(hipSetDevice(c->device));
-    const int32_t* ymap = y_idx[i]->own_contig ? nullptr : y_idx[i]->d_oid_to_lid;
-    if (tslot[i]) HIPC(hipEventRecord(tslot[i][0], c->s_main));
+    if (C.tslot[i]) HIPC(hipEventRecord(C.tslot[i][0], c->s_main));
     // interior slices (no ghost column): overlap with the halo transport
-    if (launch_phase(0, A[i], x[i]->d, y[i]->d, ymap, has_alpha, bmode, alpha, beta, dotp[i], c->s_main, fz, i)) return -1;
-    if (tslot[i]) HIPC(hipEventRecord(tslot[i][1], c->s_main));
+    if (launch_phase(C, kInterior, i, c->s_main)) return -1;
+    if (C.tslot[i]) HIPC(hipEventRecord(C.tslot[i][1], c->s_main));
     return 0;
   };
   auto boundary = [&](int i) -> int {
@@ -3795,24 +3799,11 @@ static int spmv_impl(int n, pa_mat* const A[], pa_vec* const y[], const pa_index
         launch_unpack(dt, xg[i]->n_rcv_data, xg[i]->d_lids_rcv, xg[i]->plan_fwd, PA_REPLACE,
                       xg[i]->d_buf_rcv, x[i]->d, c->s_main);
     }
-    if (tslot[i]) HIPC(hipEventRecord(tslot[i][2], c->s_main));
-    const int32_t* ymap = y_idx[i]->own_contig ? nullptr : y_idx[i]->d_oid_to_lid;
+    if (C.tslot[i]) HIPC(hipEventRecord(C.tslot[i][2], c->s_main));
     // slices reading ghosts and the side rows (after the halo)
-    if (launch_phase(1, A[i], x[i]->d, y[i]->d, ymap, has_alpha, bmode, alpha, beta, dotp[i], c->s_main, fz, i)) return -1;
-    cg_ghosts(fz, i, A[i], x[i], c->s_main);
-    // long rows (after the halo: they may read ghost columns)
-    const bool pat = knobs().spmv_format == 1 && A[i]->has_pat;
-    const int64_t long_base = A[i]->nslices + (pat ? A[i]->s_nslices + A[i]->t_nslices : 0);
-    launch_spmv_long(A[i], x[i]->d, y[i]->d, ymap, has_alpha, bmode, alpha, beta, dotp[i], long_base, c->s_main);
-    if (want_dot) {  // fold the partials (main slices, side slices, long rows) in order
-      const bool cplx = dt == PA_C64 || dt == PA_C128;
-      const int nbp = (int)(long_base + A[i]->n_long);
-      if (dot_tail)  // one part per process: the fold ends in the CG's α
-        launch_fold_cg_alpha(dt, nbp, A[i]->d_dotp, c->d_fold, c->d_result, c->d_ticket, dot_tail[i], c->s_main);
-      else
-        launch_fold(cplx, nbp, A[i]->d_dotp, c->d_fold, c->d_result, c->d_ticket, c->s_main);
-    }
-    if (tslot[i]) HIPC(hipEventRecord(tslot[i][3], c->s_main));
+    if (launch_phase(C, kBoundary, i, c->s_main)) return -1;
+    C.finish_part(i, c->s_main);
+    if (C.tslot[i]) HIPC(hipEventRecord(C.tslot[i][3], c->s_main));
     return 0;
   };
   // several parts, each with its own stream pair (one per GPU when one
@@ -3840,7 +3831,7 @@ static int spmv_impl(int n, pa_mat* const A[], pa_vec* const y[], const pa_index
   if (any_x && distinct && knobs().halo_barrier && T.pull && !T.remote) {
     pulled = true;
     pulled_on_main = knobs().halo_barrier == 2;
-    if (spmv_barrier_issue(n, x, xg, dt, T, threads, interior, boundary, pulled_on_main)) return -1;
+    if (spmv_barrier_issue(C, T, threads, interior, boundary, pulled_on_main)) return -1;
   } else if (threads && !(any_x && T.remote)) {
     if (any_x) {
       const LocalSet L = local_set(n, xg);
@@ -3876,7 +3867,7 @@ static int spmv_impl(int n, pa_mat* const A[], pa_vec* const y[], const pa_index
   }
   HIPC(hipGetLastError());
   for (int i = 0; i < n; ++i)
-    if (tslot[i]) ++A[i]->ctx->tn;
+    if (C.tslot[i]) ++A[i]->ctx->tn;
   return 0;
 }
 

@@ -229,6 +229,19 @@ constexpr int PA_GROUP_MAX = 8;
 constexpr int32_t kTriSlice = 1 << 30;  // pa_mat::d_t_len: a triple slice
 constexpr int32_t kTriPair = 1 << 29;   // pa_mat::d_t_len: a pair slice (lane l: rows a_l, a_l + 1; build_triple_sell)
 constexpr int32_t kTriLen = kTriPair - 1;  // pa_mat::d_t_len: the entries per row
+// The slice kinds of a mul!: which of a pa_mat's structures
+// and column encodings a launch entry runs.  kind_desc (pa_spmv.hip) holds
+// what each kind reads; slice_list (pa_api.cpp) a matrix's entries per phase.
+enum SliceKind : int {
+  kPattern = 0,  // pattern slices of the main structure
+  kInt32 = 1,    // int32-column slices of the main structure
+  kSide = 2,     // side SELL
+  kDelta16 = 4,  // delta16 slices of the main structure
+  kTriple = 5,   // triple SELL
+};
+// the kernels' PK / PAT template parameter: the column encoding of a wave's slice
+constexpr int kPkInt32 = 0, kPkPattern = 1, kPkDelta16 = 3, kPkTriple = 4;
+
 struct SpmvPart {
   int64_t nwork;          // slices of this part in the launch
   const int32_t* list;    // slice ids (null: 0..nwork-1)
@@ -244,8 +257,8 @@ struct SpmvPart {
   void* un = nullptr;
   void* xacc = nullptr;
   const CGState* cg = nullptr;
-  // a side-row entry (kind 2) trailing the pattern entries of one grouped
-  // launch (which 6: spmv_grouped's side tail)
+  // a side-row entry (kSide) trailing the pattern entries of one grouped
+  // kPattern launch (spmv_grouped's side tail)
   bool side = false;
 };
 
@@ -607,3 +620,20 @@ struct pa_mat {
   std::vector<int32_t> h_t_len;      // host copies for pa_mat_traffic
   void* d_dotp = nullptr;            // fused dot: one partial per (main + side + triple) slice and long row
 };
+
+namespace pa {
+// the call runs A's pattern layout: pattern, int32 and delta16 slices of the
+// main structure, the side SELL and the triple SELL (else int32 slices only)
+inline bool pattern_layout(const pa_mat* A) { return knobs().spmv_format == 1 && A->has_pat; }
+
+// The fused dot's partials in pa_mat::d_dotp: one per slice of the main
+// structure, then the side SELL's, the triple SELL's and one per long row.
+// The kernels (SpmvArgs::dot_base) and the fold (SpmvCall::finish_part) both
+// take the bases from here.
+inline int64_t dot_base(const pa_mat* A, SliceKind k) {
+  return k == kSide ? A->nslices : k == kTriple ? A->nslices + A->s_nslices : 0;
+}
+inline int64_t long_dot_base(const pa_mat* A) {
+  return pattern_layout(A) ? dot_base(A, kTriple) + A->t_nslices : A->nslices;
+}
+}  // namespace pa

@@ -1362,6 +1362,30 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void k
   group_wave<T, R, false, 0, 7, 1, true, false, true>(g);
 }
 
+// A call's (has_alpha, bmode) as the kernels' compile-time ALPHA and BMODE:
+// f(al, bm) with decltype(al)::value and decltype(bm)::value the constants
+template <typename F>
+static void with_ab(bool has_alpha, int bmode, F&& f) {
+  auto with_b = [&](auto al) {
+    if (bmode == 0) f(al, std::integral_constant<int, 0>{});
+    else if (bmode == 1) f(al, std::integral_constant<int, 1>{});
+    else f(al, std::integral_constant<int, 2>{});
+  };
+  if (has_alpha) with_b(std::true_type{});
+  else with_b(std::false_type{});
+}
+
+// a slice kind's column encoding as the kernels' compile-time PK / PAT
+// (the triple SELL holds slices of R <= 2 rows per lane only: build_triple_sell)
+template <int R, typename F>
+static void with_pk(int pk, F&& f) {
+  if (pk == kPkPattern) f(std::integral_constant<int, kPkPattern>{});
+  else if (pk == kPkDelta16) f(std::integral_constant<int, kPkDelta16>{});
+  else if (pk == kPkTriple) {
+    if constexpr (R <= 2) f(std::integral_constant<int, kPkTriple>{});
+  } else f(std::integral_constant<int, kPkInt32>{});
+}
+
 template <typename T, int R, bool ALPHA, int BMODE, int PAT>
 static void launch_group_t(const SpmvGroup<T>& g, hipStream_t st) {
   const int64_t blocks = (g.start[g.np] + 3) / 4;
@@ -1378,7 +1402,7 @@ static void launch_group_t(const SpmvGroup<T>& g, hipStream_t st) {
     }
   }
   if constexpr (PAT == 1) {
-    if (g.tail0 < g.np) {  // pattern entries, then side rows (group_which, which 6)
+    if (g.tail0 < g.np) {  // pattern entries, then side rows (SpmvPart::side, group_which)
       if constexpr (std::is_same<T, double>::value && !ALPHA && BMODE == 0) {
         bool sh7 = sh && (knobs().spmv_flags & SPMV_SHORT7) != 0 && knobs().spmv_xcd_chunk < 0;
         for (int i = 0; i < g.np && i < g.tail0; ++i) sh7 = sh7 && g.a[i].maxlen <= 7;
@@ -1412,19 +1436,6 @@ static void launch_group_t(const SpmvGroup<T>& g, hipStream_t st) {
     hipLaunchKernelGGL((k_spmv_sell_group<T, R, ALPHA, BMODE, 8, PAT>), dim3(blocks), dim3(256), 0, st, g);
 }
 
-template <typename T, int R, int PAT>
-static void launch_group_ab(const SpmvGroup<T>& g, bool has_alpha, int bmode, hipStream_t st) {
-  if (!has_alpha) {
-    if (bmode == 0) launch_group_t<T, R, false, 0, PAT>(g, st);
-    else if (bmode == 1) launch_group_t<T, R, false, 1, PAT>(g, st);
-    else launch_group_t<T, R, false, 2, PAT>(g, st);
-  } else {
-    if (bmode == 0) launch_group_t<T, R, true, 0, PAT>(g, st);
-    else if (bmode == 1) launch_group_t<T, R, true, 1, PAT>(g, st);
-    else launch_group_t<T, R, true, 2, PAT>(g, st);
-  }
-}
-
 template <typename T, int R, bool ALPHA, int BMODE, int PAT>
 static void launch_t(const SpmvArgs<T>& a, hipStream_t st) {
   const int64_t blocks = (a.nwork + 3) / 4;
@@ -1444,141 +1455,137 @@ static void launch_t(const SpmvArgs<T>& a, hipStream_t st) {
     hipLaunchKernelGGL((k_spmv_sell<T, R, ALPHA, BMODE, 8, PAT>), dim3(blocks), dim3(256), 0, st, a);
 }
 
-template <typename T, int R, int PAT>
-static void launch_ab(const SpmvArgs<T>& a, bool has_alpha, int bmode, hipStream_t st) {
-  if (!has_alpha) {
-    if (bmode == 0) launch_t<T, R, false, 0, PAT>(a, st);
-    else if (bmode == 1) launch_t<T, R, false, 1, PAT>(a, st);
-    else launch_t<T, R, false, 2, PAT>(a, st);
-  } else {
-    if (bmode == 0) launch_t<T, R, true, 0, PAT>(a, st);
-    else if (bmode == 1) launch_t<T, R, true, 1, PAT>(a, st);
-    else launch_t<T, R, true, 2, PAT>(a, st);
+// What the launches of one slice kind read from a matrix: its structure, the
+// kernels' column encoding, the longest row, where its partials of the fused
+// dot start, and whether a list of all nslices ids may be dropped (the lists
+// of the main structure are ascending subsets of 0..nslices-1)
+struct KindDesc {
+  int pk;
+  bool idlist;
+  int maxlen;
+  int64_t dot_base;
+  const int64_t* soff;
+  const int32_t* slen;
+  const int32_t* col;
+  const uint16_t* col16;
+  const int32_t* gbase;
+  const void* val;
+  const int32_t* rowmap;
+  int64_t nrows;
+};
+
+static KindDesc kind_desc(SliceKind k, const pa_mat* A) {
+  switch (k) {
+    case kPattern:
+      return {kPkPattern, true, A->maxlen_pat, 0, A->d_slice_off, A->d_plen, A->d_col, nullptr, nullptr, A->d_val,
+              nullptr, A->nrows};
+    case kDelta16:
+      return {kPkDelta16, true, A->maxlen_d16, 0, A->d_slice_off, A->d_slice_len, A->d_col, A->d_col16, A->d_gbase,
+              A->d_val, nullptr, A->nrows};
+    case kSide:
+      return {kPkInt32, false, A->maxlen_side, dot_base(A, kSide), A->d_s_off, A->d_s_len, A->d_s_col, nullptr,
+              nullptr, A->d_s_val, A->d_s_rowmap, A->s_nrows};
+    case kTriple:  // maxlen >= 9: never the short-row kernels (merged_wave)
+      return {kPkTriple, false, std::max(A->maxlen_t, 9), dot_base(A, kTriple), A->d_t_off, A->d_t_len, nullptr,
+              A->d_t_col16, A->d_t_gbase, A->d_t_val, A->d_t_rowmap, A->t_nrows};
+    case kInt32: break;
   }
+  return {kPkInt32, true, pattern_layout(A) ? A->maxlen_pm_int : A->maxlen_all, 0, A->d_slice_off, A->d_slice_len,
+          A->d_col, nullptr, nullptr, A->d_val, nullptr, A->nrows};
 }
 
-// which = 0: pattern slices of the main structure; 1: int32-column slices
-// of the main structure; 2: side SELL; 4: delta16 slices of the main
-// structure; 5: triple SELL.  list/nwork select the slices.
+// the kernel arguments of part q's slices of kind k
 template <typename T>
-static SpmvArgs<T> make_args(int which, int64_t nwork, const int32_t* list, const pa_mat* A, const void* x,
-                             void* y, const int32_t* ymap, const void* alpha, const void* beta, void* dotp,
-                             const SpmvPart* cgp = nullptr) {
+static SpmvArgs<T> make_args(SliceKind k, const SpmvPart& q, const void* alpha, const void* beta) {
+  const pa_mat* A = q.A;
+  const KindDesc d = kind_desc(k, A);
   SpmvArgs<T> a{};
-  if (cgp && cgp->cg) {
-    a.xu = (decltype(a.xu))((const T*)cgp->xu);
-    a.un = (decltype(a.un))((T*)cgp->un);
-    a.xacc = (decltype(a.xacc))((T*)cgp->xacc);
-    a.cg = (decltype(a.cg))(cgp->cg);
+  if (q.cg) {
+    a.xu = (decltype(a.xu))((const T*)q.xu);
+    a.un = (decltype(a.un))((T*)q.un);
+    a.xacc = (decltype(a.xacc))((T*)q.xacc);
+    a.cg = (decltype(a.cg))(q.cg);
   }
-  a.dotu = (decltype(a.dotu))((const T*)x);
-  a.dotp = dotp;
-  a.dot_base = which == 2 ? A->nslices : which == 5 ? A->nslices + A->s_nslices : 0;
-  a.nwork = nwork;
-  a.list = (decltype(a.list))(list);
-  a.x = (decltype(a.x))((const T*)x);
+  a.dotu = (decltype(a.dotu))((const T*)q.x);
+  a.dotp = q.dotp;
+  a.dot_base = d.dot_base;
+  a.nwork = q.nwork;
+  // every slice of the structure: without the list, one dependent load less per wave
+  const bool all = (knobs().spmv_flags & SPMV_IDLIST) && d.idlist && q.nwork == A->nslices;
+  a.list = (decltype(a.list))(all ? nullptr : q.list);
+  a.x = (decltype(a.x))((const T*)q.x);
   a.nx = A->ncols_lids;
-  a.y = (decltype(a.y))((T*)y);
-  a.ymap = (decltype(a.ymap))(ymap);
+  a.y = (decltype(a.y))((T*)q.y);
+  a.ymap = (decltype(a.ymap))(q.ymap);
   a.alpha = *(const T*)alpha;
   a.beta = *(const T*)beta;
-  a.flags = knobs().spmv_flags | (A->csr ? SPMV_PRODA : 0) | (which == 5 && (A->t_pack & 1) ? SPMV_TPACK : 0);
+  a.flags = knobs().spmv_flags | (A->csr ? SPMV_PRODA : 0) | (k == kTriple && (A->t_pack & 1) ? SPMV_TPACK : 0);
   a.xcd_chunk = knobs().spmv_xcd_chunk >= 0 ? knobs().spmv_xcd_chunk : A->xcd_auto;
-  a.maxlen = which == 0   ? A->maxlen_pat
-             : which == 2 ? A->maxlen_side
-             : which == 1 ? ((knobs().spmv_format == 1 && A->has_pat) ? A->maxlen_pm_int : A->maxlen_all)
-             : which == 4 ? A->maxlen_d16
-             : which == 5 ? std::max(A->maxlen_t, 9)  // never the short-row kernels (merged_wave)
-                          : INT32_MAX;
-  if (which == 5) {  // triple SELL
-    a.soff = (decltype(a.soff))(A->d_t_off);
-    a.slen = (decltype(a.slen))(A->d_t_len);
-    a.col16 = (decltype(a.col16))(A->d_t_col16);
-    a.gbase = (decltype(a.gbase))(A->d_t_gbase);
-    a.val = (decltype(a.val))((const T*)A->d_t_val);
-    a.rowmap = (decltype(a.rowmap))(A->d_t_rowmap);
-    a.nrows = A->t_nrows;
+  a.maxlen = d.maxlen;
+  a.soff = (decltype(a.soff))(d.soff);
+  a.slen = (decltype(a.slen))(d.slen);
+  a.col = (decltype(a.col))(d.col);
+  a.col16 = (decltype(a.col16))(d.col16);
+  a.gbase = (decltype(a.gbase))(d.gbase);
+  a.val = (decltype(a.val))((const T*)d.val);
+  a.rowmap = (decltype(a.rowmap))(d.rowmap);
+  a.nrows = d.nrows;
+  if (k == kTriple) {
     if (knobs().spmv_flags & SPMV_DESC) a.desc = (decltype(a.desc))(A->d_t_desc);
-  } else if (which == 2) {
-    a.soff = (decltype(a.soff))(A->d_s_off);
-    a.slen = (decltype(a.slen))(A->d_s_len);
-    a.col = (decltype(a.col))(A->d_s_col);
-    a.val = (decltype(a.val))((const T*)A->d_s_val);
-    a.rowmap = (decltype(a.rowmap))(A->d_s_rowmap);
-    a.nrows = A->s_nrows;
-  } else {
-    a.soff = (decltype(a.soff))(A->d_slice_off);
-    a.col = (decltype(a.col))(A->d_col);
-    a.val = (decltype(a.val))((const T*)A->d_val);
-    a.nrows = A->nrows;
-    if (which == 0) {
-      a.slen = (decltype(a.slen))(A->d_plen);
-      a.pat = (decltype(a.pat))(A->d_pat);
-      a.mask = (decltype(a.mask))(A->d_mask);
-      a.kmax = A->kmax;
-      if (knobs().spmv_flags & SPMV_DESC) a.desc = (decltype(a.desc))(A->d_pdesc);
-      if (A->d_uval && a.desc) {
-        a.uval = (decltype(a.uval))((const T*)A->d_uval);
-        a.uK = A->uK;
-        for (int e = 0; e < 8; ++e) a.upat[e] = A->upat[e];
-      }
-    } else {
-      a.slen = (decltype(a.slen))(A->d_slice_len);
-      if (which == 4) {
-        a.col16 = (decltype(a.col16))(A->d_col16);
-        a.gbase = (decltype(a.gbase))(A->d_gbase);
-      }
+  } else if (k == kPattern) {
+    a.pat = (decltype(a.pat))(A->d_pat);
+    a.mask = (decltype(a.mask))(A->d_mask);
+    a.kmax = A->kmax;
+    if (knobs().spmv_flags & SPMV_DESC) a.desc = (decltype(a.desc))(A->d_pdesc);
+    if (A->d_uval && a.desc) {
+      a.uval = (decltype(a.uval))((const T*)A->d_uval);
+      a.uK = A->uK;
+      for (int e = 0; e < 8; ++e) a.upat[e] = A->upat[e];
     }
-  }
-  if (which == 1) {
+  } else if (k == kInt32) {
     a.sflags = (decltype(a.sflags))(A->d_sflags);
     a.lmask = (decltype(a.lmask))(A->d_lmask);
     // spmv_format 0 runs the delta16 slices (Float32: interleaved rows) as int32
-    if (A->d_col16 && A->R == 4 && !(knobs().spmv_format == 1 && A->has_pat)) a.ilv = (decltype(a.ilv))(A->d_kind);
+    if (A->d_col16 && A->R == 4 && !pattern_layout(A)) a.ilv = (decltype(a.ilv))(A->d_kind);
   }
   return a;
 }
 
 template <typename T, int R>
-static void launch_which(int which, int64_t nwork, const int32_t* list, const pa_mat* A, const void* x,
-                         void* y, const int32_t* ymap, bool has_alpha, int bmode, const void* alpha,
-                         const void* beta, void* dotp, hipStream_t st, const SpmvPart* cgp) {
-  const SpmvArgs<T> a = make_args<T>(which, nwork, list, A, x, y, ymap, alpha, beta, dotp, cgp);
-  if (which == 0) launch_ab<T, R, 1>(a, has_alpha, bmode, st);
-  else if (which == 4) launch_ab<T, R, 3>(a, has_alpha, bmode, st);
-  else if (which == 5) {
-    if constexpr (R <= 2) launch_ab<T, R, 4>(a, has_alpha, bmode, st);  // (build_triple_sell: R <= 2 only)
-  } else launch_ab<T, R, 0>(a, has_alpha, bmode, st);
+static void launch_which(SliceKind k, const SpmvPart& q, bool has_alpha, int bmode, const void* alpha,
+                         const void* beta, hipStream_t st) {
+  const SpmvArgs<T> a = make_args<T>(k, q, alpha, beta);
+  with_pk<R>(kind_desc(k, q.A).pk, [&](auto pk) {
+    with_ab(has_alpha, bmode, [&](auto al, auto bm) {
+      launch_t<T, R, decltype(al)::value, decltype(bm)::value, decltype(pk)::value>(a, st);
+    });
+  });
 }
 
-// the same slices of np parts as one launch per PA_GROUP_MAX parts
+// the same slices of np parts as one launch per PA_GROUP_MAX parts; entries
+// marked SpmvPart::side are side rows trailing the pattern entries of a
+// kPattern call (the caller passes at most PA_GROUP_MAX entries, pattern ones
+// first): one TAIL launch
 template <typename T, int R>
-static void group_which(int which, int np, const SpmvPart* parts, bool has_alpha, int bmode, const void* alpha,
+static void group_which(SliceKind kind, int np, const SpmvPart* parts, bool has_alpha, int bmode, const void* alpha,
                         const void* beta, hipStream_t st) {
-  // which 6: pattern entries followed by side-row entries (SpmvPart::side;
-  // the caller passes at most PA_GROUP_MAX entries, pattern ones first): one
-  // TAIL launch
   SpmvGroup<T> g{};
   g.tail0 = PA_GROUP_MAX + 1;
   auto flush = [&]() {
     if (g.np == 0) return;
-    if (which == 0 || which == 6) launch_group_ab<T, R, 1>(g, has_alpha, bmode, st);
-    else if (which == 4) launch_group_ab<T, R, 3>(g, has_alpha, bmode, st);
-    else if (which == 5) {
-      if constexpr (R <= 2) launch_group_ab<T, R, 4>(g, has_alpha, bmode, st);  // (R <= 2 only)
-    }
-    else launch_group_ab<T, R, 0>(g, has_alpha, bmode, st);
+    with_pk<R>(kind_desc(kind, parts[0].A).pk, [&](auto pk) {
+      with_ab(has_alpha, bmode, [&](auto al, auto bm) {
+        launch_group_t<T, R, decltype(al)::value, decltype(bm)::value, decltype(pk)::value>(g, st);
+      });
+    });
     g = SpmvGroup<T>{};
     g.tail0 = PA_GROUP_MAX + 1;
   };
   for (int i = 0; i < np; ++i) {
     const SpmvPart& q = parts[i];
     if (q.nwork <= 0) continue;
-    const int kind = which == 6 ? (q.side ? 2 : 0) : which;
-    if (which == 6 && q.side && g.tail0 > g.np) g.tail0 = g.np;
-    const int32_t* list = q.list;
-    if ((knobs().spmv_flags & SPMV_IDLIST) && list && kind != 2 && kind != 5 && q.nwork == q.A->nslices) list = nullptr;
-    g.a[g.np] = make_args<T>(kind, q.nwork, list, q.A, q.x, q.y, q.ymap, alpha, beta, q.dotp, &q);
+    if (q.side && g.tail0 > g.np) g.tail0 = g.np;
+    g.a[g.np] = make_args<T>(q.side ? kSide : kind, q, alpha, beta);
     g.start[g.np + 1] = g.start[g.np] + q.nwork;
     if (++g.np == PA_GROUP_MAX) flush();
   }
@@ -1587,15 +1594,14 @@ static void group_which(int which, int np, const SpmvPart* parts, bool has_alpha
 
 // the per-element-type entry points (one translation unit each, PA_SPMV_DT)
 #define PA_DT_DECL(k)                                                                                          \
-  void spmv_group_##k(int which, int np, const SpmvPart* parts, bool has_alpha, int bmode, const void* alpha,  \
+  void spmv_group_##k(SliceKind kind, int np, const SpmvPart* parts, bool has_alpha, int bmode, const void* alpha,  \
                       const void* beta, hipStream_t st);                                                        \
-  int spmv_merged_##k(int n, const int* which, const SpmvPart* parts, bool has_alpha, int bmode,              \
+  int spmv_merged_##k(int n, const SliceKind* kinds, const SpmvPart* parts, bool has_alpha, int bmode,      \
                       const void* alpha, const void* beta, pa_ctx* owner, hipStream_t st);                     \
   void spmv_long_##k(const pa_mat* A, const void* x, void* y, const int32_t* ymap, bool has_alpha, int bmode,  \
                      const void* alpha, const void* beta, void* dotp, int64_t dot_base, hipStream_t st);       \
-  void spmv_part_##k(int which, int64_t nwork, const int32_t* list, const pa_mat* A, const void* x, void* y,  \
-                     const int32_t* ymap, bool has_alpha, int bmode, const void* alpha, const void* beta,     \
-                     void* dotp, hipStream_t st, const SpmvPart* cgp);
+  void spmv_part_##k(SliceKind kind, const SpmvPart& q, bool has_alpha, int bmode, const void* alpha,         \
+                     const void* beta, hipStream_t st);
 PA_DT_DECL(0)
 PA_DT_DECL(1)
 PA_DT_DECL(2)
@@ -1618,25 +1624,25 @@ constexpr int kDtR = 1;
 // Float32 matrices hold 4 or 2 rows per lane (pa_tune "f32_rows", fixed when
 // a matrix is built): a call's parts run as runs of equal R
 constexpr bool kDtR2 = PA_SPMV_DT == 0;
-void PA_CAT(spmv_group_, PA_SPMV_DT)(int which, int np, const SpmvPart* parts, bool has_alpha, int bmode,
+void PA_CAT(spmv_group_, PA_SPMV_DT)(SliceKind kind, int np, const SpmvPart* parts, bool has_alpha, int bmode,
                                      const void* alpha, const void* beta, hipStream_t st) {
   if constexpr (kDtR2) {
     for (int i = 0; i < np;) {
       int j = i + 1;
       while (j < np && parts[j].A->R == parts[i].A->R) ++j;
-      if (parts[i].A->R == 2) group_which<DtT, 2>(which, j - i, parts + i, has_alpha, bmode, alpha, beta, st);
-      else group_which<DtT, kDtR>(which, j - i, parts + i, has_alpha, bmode, alpha, beta, st);
+      if (parts[i].A->R == 2) group_which<DtT, 2>(kind, j - i, parts + i, has_alpha, bmode, alpha, beta, st);
+      else group_which<DtT, kDtR>(kind, j - i, parts + i, has_alpha, bmode, alpha, beta, st);
       i = j;
     }
   } else {
-    group_which<DtT, kDtR>(which, np, parts, has_alpha, bmode, alpha, beta, st);
+    group_which<DtT, kDtR>(kind, np, parts, has_alpha, bmode, alpha, beta, st);
   }
 }
 #else
-void launch_spmv_group(int which, int np, const SpmvPart* parts, bool has_alpha, int bmode, const void* alpha,
+void launch_spmv_group(SliceKind kind, int np, const SpmvPart* parts, bool has_alpha, int bmode, const void* alpha,
                        const void* beta, hipStream_t st) {
   if (np <= 0) return;
-#define spmv_group_(k) spmv_group_##k(which, np, parts, has_alpha, bmode, alpha, beta, st)
+#define spmv_group_(k) spmv_group_##k(kind, np, parts, has_alpha, bmode, alpha, beta, st)
   switch (parts[0].A->dtype) {
     case PA_F32: spmv_group_(0); break;
     case PA_F64: spmv_group_(1); break;
@@ -1688,16 +1694,16 @@ __device__ __forceinline__ void merged_wave(const SpmvTable<T>* __restrict__ tab
   const int pk = __builtin_amdgcn_readfirstlane(tab->pk[p]);
   const int64_t lw = w - tab->start[p];
   const SpmvArgs<T>& a = tab->a[p];
-  if (pk == 1) spmv_wave<T, R, ALPHA, BMODE, U, 1, SH, XV>(a, lw);
-  else if (pk == 3) spmv_wave<T, R, ALPHA, BMODE, U, 3, SH, XV>(a, lw);
-  else if (pk == 4) {
+  if (pk == kPkPattern) spmv_wave<T, R, ALPHA, BMODE, U, kPkPattern, SH, XV>(a, lw);
+  else if (pk == kPkDelta16) spmv_wave<T, R, ALPHA, BMODE, U, kPkDelta16, SH, XV>(a, lw);
+  else if (pk == kPkTriple) {
     // the triple SELL never runs in the short-row (make_args: maxlen >= 9)
     // or fused-u kernels (pa_cg_solve_all: no fused update with it): their
     // registers stay those of the other kinds
     // (and slices of R <= 2 rows per lane only: build_triple_sell)
-    if constexpr (!SH && !XV && R <= 2) spmv_wave<T, R, ALPHA, BMODE, U, 4, SH, XV>(a, lw);
+    if constexpr (!SH && !XV && R <= 2) spmv_wave<T, R, ALPHA, BMODE, U, kPkTriple, SH, XV>(a, lw);
   }
-  else spmv_wave<T, R, ALPHA, BMODE, U, 0, SH, XV>(a, lw);
+  else spmv_wave<T, R, ALPHA, BMODE, U, kPkInt32, SH, XV>(a, lw);
 }
 
 // No occupancy cap: amdgpu_waves_per_eu(4) (F32 134 -> 128 VGPRs, a small
@@ -1736,8 +1742,6 @@ static void launch_merged_t(const SpmvTable<T>* d, int n, int64_t waves, bool sh
     hipLaunchKernelGGL((k_spmv_merged<T, R, ALPHA, BMODE, 8, false>), dim3(blocks), dim3(256), 0, st, d, n, waves, xc);
 }
 
-static int pk_of(int which) { return which == 0 ? 1 : which == 4 ? 3 : which == 5 ? 4 : 0; }
-
 // One merged launch, prepared: its device table (cached) and launch shape
 template <typename T>
 struct MergedLaunch {
@@ -1748,8 +1752,8 @@ struct MergedLaunch {
 };
 
 template <typename T, int R>
-static int merged_prepare(int n, const int* which, const SpmvPart* parts, bool has_alpha, int bmode,
-                          const void* alpha, const void* beta, pa_ctx* owner, hipStream_t st, MergedLaunch<T>* out) {
+static int merged_prepare(int n, const SliceKind* kinds, const SpmvPart* parts, const void* alpha, const void* beta,
+                          pa_ctx* owner, hipStream_t st, MergedLaunch<T>* out) {
   // the table's used bytes (header + n entries) are its cache key: only
   // those are zeroed, compared and uploaded (a 48-entry table is ≈15 KB, a
   // call's tables hold 1-4 entries: per-call host work of the stream-pair
@@ -1762,10 +1766,8 @@ static int merged_prepare(int n, const int* which, const SpmvPart* parts, bool h
     const SpmvPart& q = parts[i];
     if (q.nwork <= 0) continue;
     if (h.n == kMergeMax) return 1;
-    const int32_t* list = q.list;
-    if ((knobs().spmv_flags & SPMV_IDLIST) && list && which[i] != 2 && which[i] != 5 && q.nwork == q.A->nslices) list = nullptr;
-    h.a[h.n] = make_args<T>(which[i], q.nwork, list, q.A, q.x, q.y, q.ymap, alpha, beta, q.dotp, &q);
-    h.pk[h.n] = pk_of(which[i]);
+    h.a[h.n] = make_args<T>(kinds[i], q, alpha, beta);
+    h.pk[h.n] = kind_desc(kinds[i], q.A).pk;
     sh = sh && h.a[h.n].maxlen <= 8;
     h.start[h.n + 1] = h.start[h.n] + q.nwork;
     ++h.n;
@@ -1821,67 +1823,59 @@ static void merged_launch(const MergedLaunch<T>& m, bool has_alpha, int bmode, h
     else hipLaunchKernelGGL((k_spmv_merged<T, R, false, 0, 8, false, true>), dim3(blocks), dim3(256), 0, st, m.dt, m.n, m.waves, xc);
     return;
   }
-  if (!has_alpha) {
-    if (bmode == 0) launch_merged_t<T, R, false, 0>(m.dt, m.n, m.waves, m.sh, st);
-    else if (bmode == 1) launch_merged_t<T, R, false, 1>(m.dt, m.n, m.waves, m.sh, st);
-    else launch_merged_t<T, R, false, 2>(m.dt, m.n, m.waves, m.sh, st);
-  } else {
-    if (bmode == 0) launch_merged_t<T, R, true, 0>(m.dt, m.n, m.waves, m.sh, st);
-    else if (bmode == 1) launch_merged_t<T, R, true, 1>(m.dt, m.n, m.waves, m.sh, st);
-    else launch_merged_t<T, R, true, 2>(m.dt, m.n, m.waves, m.sh, st);
-  }
+  with_ab(has_alpha, bmode, [&](auto al, auto bm) {
+    launch_merged_t<T, R, decltype(al)::value, decltype(bm)::value>(m.dt, m.n, m.waves, m.sh, st);
+  });
 }
 
 template <typename T, int R>
-static int merged_t(int n, const int* which, const SpmvPart* parts, bool has_alpha, int bmode, const void* alpha,
-                    const void* beta, pa_ctx* owner, hipStream_t st) {
+static int merged_t(int n, const SliceKind* kinds, const SpmvPart* parts, bool has_alpha, int bmode,
+                    const void* alpha, const void* beta, pa_ctx* owner, hipStream_t st) {
   MergedLaunch<T> m;
-  const int rc = merged_prepare<T, R>(n, which, parts, has_alpha, bmode, alpha, beta, owner, st, &m);
+  const int rc = merged_prepare<T, R>(n, kinds, parts, alpha, beta, owner, st, &m);
   if (rc) return rc;
   merged_launch<T, R>(m, has_alpha, bmode, st);
   return 0;
 }
 
-// n (which, part) entries as one launch; returns 1 when they do not fit one
+// n (kind, part) entries as one launch; returns 1 when they do not fit one
 // table (the caller launches per kind), -1 on an allocation/copy error
 #if defined(PA_SPMV_DT)
-int PA_CAT(spmv_merged_, PA_SPMV_DT)(int n, const int* which, const SpmvPart* parts, bool has_alpha, int bmode,
-                                     const void* alpha, const void* beta, pa_ctx* owner, hipStream_t st) {
+int PA_CAT(spmv_merged_, PA_SPMV_DT)(int n, const SliceKind* kinds, const SpmvPart* parts, bool has_alpha,
+                                     int bmode, const void* alpha, const void* beta, pa_ctx* owner, hipStream_t st) {
   if constexpr (kDtR2) {
     bool mixed = false;
     for (int i = 1; i < n; ++i) mixed = mixed || parts[i].A->R != parts[0].A->R;
     if (mixed) {  // parts of both layouts: one merged launch per layout
       if (n > kMergeMax) return 1;  // (nothing launched: the caller runs per kind)
-      std::vector<int> w[2];
+      std::vector<SliceKind> w[2];
       std::vector<SpmvPart> q[2];
       for (int i = 0; i < n; ++i) {
         const int k = parts[i].A->R == 2 ? 0 : 1;
-        w[k].push_back(which[i]);
+        w[k].push_back(kinds[i]);
         q[k].push_back(parts[i]);
       }
       // both tables before either launch: a table that does not fit or
       // fails leaves nothing launched for the caller's per-kind fallback to
       // repeat (with β ≠ 0, y would accumulate twice)
       MergedLaunch<DtT> m2, m4;
-      int rc = merged_prepare<DtT, 2>((int)w[0].size(), w[0].data(), q[0].data(), has_alpha, bmode, alpha, beta,
-                                      owner, st, &m2);
+      int rc = merged_prepare<DtT, 2>((int)w[0].size(), w[0].data(), q[0].data(), alpha, beta, owner, st, &m2);
       if (rc == 0)
-        rc = merged_prepare<DtT, kDtR>((int)w[1].size(), w[1].data(), q[1].data(), has_alpha, bmode, alpha, beta,
-                                       owner, st, &m4);
+        rc = merged_prepare<DtT, kDtR>((int)w[1].size(), w[1].data(), q[1].data(), alpha, beta, owner, st, &m4);
       if (rc) return rc;
       merged_launch<DtT, 2>(m2, has_alpha, bmode, st);
       merged_launch<DtT, kDtR>(m4, has_alpha, bmode, st);
       return 0;
     }
-    if (n > 0 && parts[0].A->R == 2) return merged_t<DtT, 2>(n, which, parts, has_alpha, bmode, alpha, beta, owner, st);
+    if (n > 0 && parts[0].A->R == 2) return merged_t<DtT, 2>(n, kinds, parts, has_alpha, bmode, alpha, beta, owner, st);
   }
-  return merged_t<DtT, kDtR>(n, which, parts, has_alpha, bmode, alpha, beta, owner, st);
+  return merged_t<DtT, kDtR>(n, kinds, parts, has_alpha, bmode, alpha, beta, owner, st);
 }
 #else
-int launch_spmv_merged(int n, const int* which, const SpmvPart* parts, bool has_alpha, int bmode,
+int launch_spmv_merged(int n, const SliceKind* kinds, const SpmvPart* parts, bool has_alpha, int bmode,
                        const void* alpha, const void* beta, pa_ctx* owner, hipStream_t st) {
   if (n <= 0) return 0;
-#define spmv_merged_(k) spmv_merged_##k(n, which, parts, has_alpha, bmode, alpha, beta, owner, st)
+#define spmv_merged_(k) spmv_merged_##k(n, kinds, parts, has_alpha, bmode, alpha, beta, owner, st)
   switch (parts[0].A->dtype) {
     case PA_F32: return spmv_merged_(0);
     case PA_F64: return spmv_merged_(1);
@@ -2056,13 +2050,9 @@ static void long_t(const pa_mat* A, const void* x, void* y, const int32_t* ymap,
 template <typename T>
 static void long_ab(const pa_mat* A, const void* x, void* y, const int32_t* ymap, bool has_alpha, int bmode,
                     const void* alpha, const void* beta, void* dotp, int64_t dot_base, hipStream_t st) {
-#define PA_L(AL, BM) long_t<T, AL, BM>(A, x, y, ymap, alpha, beta, dotp, dot_base, st)
-  if (!has_alpha) {
-    if (bmode == 0) PA_L(false, 0); else if (bmode == 1) PA_L(false, 1); else PA_L(false, 2);
-  } else {
-    if (bmode == 0) PA_L(true, 0); else if (bmode == 1) PA_L(true, 1); else PA_L(true, 2);
-  }
-#undef PA_L
+  with_ab(has_alpha, bmode, [&](auto al, auto bm) {
+    long_t<T, decltype(al)::value, decltype(bm)::value>(A, x, y, ymap, alpha, beta, dotp, dot_base, st);
+  });
 }
 
 // dotp: partial of long row w at dotp[dot_base + w] (the fused CG dot)
@@ -2072,16 +2062,15 @@ void PA_CAT(spmv_long_, PA_SPMV_DT)(const pa_mat* A, const void* x, void* y, con
                                     hipStream_t st) {
   long_ab<DtT>(A, x, y, ymap, has_alpha, bmode, alpha, beta, dotp, dot_base, st);
 }
-void PA_CAT(spmv_part_, PA_SPMV_DT)(int which, int64_t nwork, const int32_t* list, const pa_mat* A, const void* x,
-                                    void* y, const int32_t* ymap, bool has_alpha, int bmode, const void* alpha,
-                                    const void* beta, void* dotp, hipStream_t st, const SpmvPart* cgp) {
+void PA_CAT(spmv_part_, PA_SPMV_DT)(SliceKind kind, const SpmvPart& q, bool has_alpha, int bmode, const void* alpha,
+                                    const void* beta, hipStream_t st) {
   if constexpr (kDtR2) {
-    if (A->R == 2) {
-      launch_which<DtT, 2>(which, nwork, list, A, x, y, ymap, has_alpha, bmode, alpha, beta, dotp, st, cgp);
+    if (q.A->R == 2) {
+      launch_which<DtT, 2>(kind, q, has_alpha, bmode, alpha, beta, st);
       return;
     }
   }
-  launch_which<DtT, kDtR>(which, nwork, list, A, x, y, ymap, has_alpha, bmode, alpha, beta, dotp, st, cgp);
+  launch_which<DtT, kDtR>(kind, q, has_alpha, bmode, alpha, beta, st);
 }
 #else
 // dotp: partial of long row w at dotp[dot_base + w] (the fused CG dot)
@@ -2098,14 +2087,11 @@ void launch_spmv_long(const pa_mat* A, const void* x, void* y, const int32_t* ym
 #undef spmv_long_
 }
 
-void launch_spmv_part(int which, int64_t nwork, const int32_t* list, const pa_mat* A, const void* x,
-                      void* y, const int32_t* ymap, bool has_alpha, int bmode, const void* alpha,
-                      const void* beta, void* dotp, hipStream_t st, const SpmvPart* cgp) {
-  // a slice list as long as the structure is 0..nslices-1 (lists are
-  // ascending subsets): launch without it, one dependent load less per wave
-  if ((knobs().spmv_flags & SPMV_IDLIST) && list && which != 2 && which != 5 && nwork == A->nslices) list = nullptr;
-#define spmv_part_(k) spmv_part_##k(which, nwork, list, A, x, y, ymap, has_alpha, bmode, alpha, beta, dotp, st, cgp)
-  switch (A->dtype) {
+// one part's slices of one kind as a launch of their own
+void launch_spmv_part(SliceKind kind, const SpmvPart& q, bool has_alpha, int bmode, const void* alpha,
+                      const void* beta, hipStream_t st) {
+#define spmv_part_(k) spmv_part_##k(kind, q, has_alpha, bmode, alpha, beta, st)
+  switch (q.A->dtype) {
     case PA_F32: spmv_part_(0); break;
     case PA_F64: spmv_part_(1); break;
     case PA_C64: spmv_part_(2); break;

@@ -246,6 +246,47 @@ def test_launch_paths_equal_oracle(be, pamd, O, merge, direct, d16):
 
 
 
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_own_stream_pairs_irregular_equal_oracle(pamd, O, dtype):
+    """Every part its own stream pair (the barrier issue, one launch set per
+    part and phase) on Voronoi parts: triple-SELL / delta16 slices and side
+    rows in one part, so every kind's dot base and the end of a part run.
+    mul! with α ≠ 1, then with β ≠ 0, then the fused mul! + dot: y and the
+    ghosts of x equal the oracle's bits, the dot to 1e-12."""
+    be = pamd.HIPBackend(devices=[0], share_streams=False)
+    N, nparts = (30, 28, 26), 4
+    parts = be.get_part_ids(nparts)
+    A = pamd.drivers.irregular_problem(parts, N, 27, dtype)
+    assert any(i["triple_sell_slices"] + i["delta16_slices"] > 0 and i["side_rows"] > 0 for i in A.info().parts)
+    OA = _oracle(O, N, nparts, dtype)
+    rng = np.random.default_rng(SEED + 51)
+    xs = {p: _rand(rng, A.cols.partition.local(p).num_lids, dtype) for p in parts.part_ids}
+    x = pamd.PVector.from_host(pamd.map_parts(lambda s: xs[s.part], A.cols.partition), A.cols)
+    y = pamd.PVector.undef(A.rows, dtype)
+    ox = O.PVector(O.map_parts(lambda s: _ox(O, xs[s.part]), OA.cols.partition), OA.cols)
+    oy = O.pvector_undef(OA.rows, dtype)
+    sc = np.dtype(dtype).type
+
+    def same(what):
+        got, gx = y.to_host(), x.to_host()
+        for p in parts.part_ids:
+            assert _eq(O, got.local(p), oy.values[p]), f"part {p}: {what} differs"
+            assert _eq(O, gx.local(p), ox.values[p]), f"part {p}: ghost values of x differ ({what})"
+
+    pamd.mul_(y, A, x, 2.0, 0.0)
+    O.mul_(oy, OA, ox, sc(2.0), 0.0)
+    same("mul!(α = 2)")
+    pamd.mul_(y, A, x, 0.75, -2.0)
+    O.mul_(oy, OA, ox, sc(0.75), sc(-2.0))
+    same("mul!(α = 0.75, β = -2)")
+    d = pamd.mul_dot_(y, A, x)
+    O.mul_(oy, OA, ox)
+    same("mul! of the fused dot")
+    od = O.dot(ox, oy)
+    print(f"dot {d!r} oracle {od!r} rel {abs(d - od) / abs(od):.3e}")
+    assert abs(d - od) <= 1e-12 * abs(od)
+
+
 @pytest.mark.parametrize("dtype", [np.float64, np.float32, np.complex64, np.complex128])
 @pytest.mark.parametrize("d16,tri16", [(1, 1), (1, 0), (0, 0)])
 @pytest.mark.parametrize("tail", [8, 0])
