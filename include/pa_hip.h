@@ -281,6 +281,93 @@ int pa_vec_copy(pa_vec* dst, const pa_index* idx_dst,
 int pa_vec_axpby(pa_vec* y, const pa_vec* x, const pa_index* idx,
                  const void* a, int mode, int all_lids);
 
+/* ---- broadcast expressions (Interfaces.jl:1688-1765) --------------------
+ * Any elementwise expression over PVectors and numbers as one pass: a
+ * postfix program over at most PA_EXPR_MAX_VECS vector operands and
+ * PA_EXPR_MAX_SCALARS scalars, at most PA_EXPR_MAX_OPS ops, evaluated per
+ * element on an operand stack of PA_EXPR_MAX_DEPTH slots, then stored
+ * (pa_vec_eval) or reduced (pa_reduce_expr_all).
+ *
+ * Op codes: PA_OP_VEC pushes element i of vector `arg`, PA_OP_SCAL pushes
+ * scalar `arg`; the binary ops ADD SUB MUL DIV and the comparisons (1 or 0
+ * of the node's type) take their operands as the mode bits of `flags` say:
+ * PA_EXPR_SS below ∘ top (both popped), PA_EXPR_RS top ∘ below (the
+ * reversed forms RSUB / RDIV: sibling subtrees are pure, so the encoder
+ * emits the deeper one first and the depth stays minimal), PA_EXPR_SC
+ * top ∘ scalar `arg`, PA_EXPR_CS scalar `arg` ∘ top (scalars as immediates:
+ * no stack slot).  NEG ABS ABS2 CONJ replace the top.
+ *
+ * Types follow Julia's broadcast.  All vectors and y share one dtype T.
+ * scalar_kinds[k]: 0 a value of T, 1 a Float64, 2 a ComplexF64 (complex T
+ * only; into a real vector it is an InexactError), 3 a value of real(T) (an
+ * Int or a Float32 next to ComplexF32 vectors: Julia's Real ∘ Complex
+ * methods apply; with real T the same as 0); scalars holds one 16-byte
+ * slot per scalar with the value of that type at offset 0.  A node is of T
+ * unless an operand is a Float64 / ComplexF64 scalar or a wide node: then it
+ * is of wide_of<T> (Float64 / ComplexF64) and its op carries PA_EXPR_WIDE;
+ * a T op is evaluated in T, a wide op in the wide type, and the result is
+ * rounded to T once on the store ((v .+ u) .* 2.0 with Float32 v, u adds in
+ * Float32 and multiplies in Float64).  With complex T a node may be real
+ * valued (a Float64 or real(T) scalar, abs2, a comparison): PA_EXPR_LREAL /
+ * PA_EXPR_RREAL mark a real left / right operand (unary ops: LREAL), and the
+ * op is Julia's Real ∘ Complex method (componentwise product, the imaginary
+ * part kept by + and -).  DIV, ABS and the ordered comparisons take real
+ * operands only; EQ and NE also complex ones.  A comparison's 1 / 0 is a
+ * node of T whatever its operands' types (Julia's Bool takes the other
+ * operand's type in arithmetic); its op still carries its operands' tags.  The tags must equal what
+ * these rules infer (pa_expr_check), anything else is rejected.            */
+#define PA_EXPR_MAX_OPS 32
+#define PA_EXPR_MAX_VECS 8
+#define PA_EXPR_MAX_SCALARS 8
+#define PA_EXPR_MAX_DEPTH 4
+enum { PA_OP_VEC = 0, PA_OP_SCAL = 1, PA_OP_ADD = 2, PA_OP_SUB = 3, PA_OP_MUL = 4, PA_OP_DIV = 5,
+       PA_OP_NEG = 6, PA_OP_ABS = 7, PA_OP_ABS2 = 8, PA_OP_CONJ = 9, PA_OP_LT = 10, PA_OP_LE = 11,
+       PA_OP_GT = 12, PA_OP_GE = 13, PA_OP_EQ = 14, PA_OP_NE = 15 };
+enum { PA_EXPR_WIDE = 1, PA_EXPR_LREAL = 2, PA_EXPR_RREAL = 4,
+       PA_EXPR_SS = 0, PA_EXPR_SC = 8, PA_EXPR_CS = 16, PA_EXPR_RS = 24, PA_EXPR_MODE = 24 };
+enum { PA_REDUCE_SUM = 0, PA_REDUCE_MAX = 1, PA_REDUCE_MIN = 2 };
+typedef struct pa_expr_op {
+  uint8_t code;   /* PA_OP_* */
+  uint8_t arg;    /* vector or scalar number */
+  uint8_t flags;  /* PA_EXPR_WIDE | _LREAL | _RREAL | operand mode */
+  uint8_t pad;    /* 0 */
+} pa_expr_op;
+typedef struct pa_expr {
+  int32_t nops;
+  pa_expr_op ops[PA_EXPR_MAX_OPS];
+} pa_expr;
+/* The checks pa_vec_eval / pa_reduce_expr_all run on a program before any
+ * launch (no device needed): op codes, operand numbers, stack depth, the
+ * type rules above.  *depth (optional) gets the stack depth the program
+ * needs, *result_flags (optional) the root's PA_EXPR_WIDE / PA_EXPR_LREAL. */
+int pa_expr_check(const pa_expr* prog, int dtype, int nvec, int nscal, const int* scalar_kinds,
+                  int* depth, int* result_flags);
+/* materialize!(y, bc) for one part (Interfaces.jl:1710-1720): y[i] =
+ * prog(v[0][i], ..) over every lid when all_lids != 0 (every operand then
+ * has y's length: the host passes it when all share y's partition object,
+ * a.rows === b.rows at 1714 and 1730), else over the owned values, y and
+ * each operand addressed through its own index set (equal owned counts;
+ * ghosts of y untouched).  y may be one of the operands (same-index access).
+ * Identity-addressed operands (all lids, or contiguous owned lids everywhere)
+ * stream 16 B per lane and operand; otherwise one element per lane gathers
+ * through the oid → lid tables.                                             */
+int pa_vec_eval(pa_vec* y, const pa_index* y_idx, const pa_expr* prog, int nvec,
+                const pa_vec* const v[], const pa_index* const v_idx[], int nscal,
+                const void* scalars, const int* scalar_kinds, int all_lids);
+/* The expression reduced over the owned values of the n local parts
+ * (v[i * nvec + k], v_idx[i * nvec + k]: operand k of part i).
+ * PA_REDUCE_SUM: sum(bc) as pa_sum_all (Interfaces.jl:1973-1983): Float64 /
+ * ComplexF64 accumulator per part, each part's value rounded to T, parts
+ * added in T in part order; result: host scalar of T.  PA_REDUCE_MAX / _MIN:
+ * maximum / minimum (Interfaces.jl:1841-1863), real-valued expressions only,
+ * init -Inf / +Inf (typemin / typemax; what a part without owned values
+ * contributes), a NaN in any owned element gives NaN; result: host double.
+ * With 0/1-valued expressions these are any / all (1827-1839), == (1682-1686),
+ * and with abs / abs2 the norms and Distances metrics (1767-1817).          */
+int pa_reduce_expr_all(int n, int kind, const pa_expr* prog, int nvec,
+                       const pa_vec* const v[], const pa_index* const v_idx[], int nscal,
+                       const void* scalars, const int* scalar_kinds, void* result);
+
 /* ---- matrices (one part of a PSparseMatrix) ----------------------------
  * From the reference's local SparseMatrixCSC (1-based colptr/rowval with
  * index_bytes = 4 or 8, nzval of dtype), with the matrix's rows/cols index

@@ -14,7 +14,10 @@
 #   * specialisations of the hot path for PVector/PSparseMatrix over HIPData:
 #     mul! (Interfaces.jl:2246), exchange!/assemble! of vectors (2071-2106)
 #     and matrices (2375-2404), dot/norm/sum (1767, 1973-1992), copyto!/
-#     copy!/fill!/rmul! (1649-1680, 1966), the CG broadcasts (1688-1765) and
+#     copy!/fill!/rmul! (1649-1680, 1966), broadcasts (1688-1765: the CG
+#     patterns by name, any other tree of + - * / abs abs2 conj and
+#     comparisons as one pa_vec_eval pass), ==, maximum / minimum, sum of a
+#     broadcast, the Euclidean distances (1682-1686, 1774-1863),
 #     IterativeSolvers.cg! (v0.9, test_fdm.jl:115), and the COO triplet
 #     exchange assemble!(I, J, V, rows) (2406-2492);
 #   * everything else (PRange, Exchanger, add_gids!, gather/scatter setup
@@ -33,6 +36,7 @@ using LinearAlgebra
 using SparseArrays
 using SparseMatricesCSR
 import IterativeSolvers
+import Distances
 import PartitionedArrays: get_part_ids, map_parts, i_am_main, get_backend, get_part, gather!,
   gather_all!, scatter, async_exchange!, async_assemble!, num_parts, prun_debug, PVector,
   PSparseMatrix, PRange, SequentialData, AbstractPData, AbstractBackend, Table, Exchanger, MAIN,
@@ -570,6 +574,9 @@ function LinearAlgebra.dot(a::HIPVector{T}, b::HIPVector{T}) where {T<:DeviceElt
   r[]
 end
 function LinearAlgebra.norm(a::HIPVector{T}, p::Real=2) where {T<:DeviceEltype}
+  # p = 1 and p = Inf of real vectors: sum(abs.(a)) and maximum(abs, a) in one pass
+  p == 1 && T <: Real && return sum(_expr_node(abs, a))
+  p == Inf && T <: Real && return maximum(abs, a)
   p == 2 || return invoke(norm, Tuple{PVector,Real}, a, p)
   r = Ref{Float64}(0.0)
   check(ccall((:pa_norm2_all, libpa), Cint, (Cint, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ref{Float64}),
@@ -648,8 +655,10 @@ end
 LinearAlgebra.rmul!(a::HIPVector{T}, v::Number) where {T<:DeviceEltype} = _axpby!(a, nothing, v, 4)
 
 # Broadcasts: a lazy tree over HIP vectors; materialize! runs the patterns of
-# the CG recurrence on the device (pa_vec_axpby modes 0-3, copies) and any
-# other expression through the reference's host broadcast on synced parts.
+# the CG recurrence on the device by name (pa_vec_axpby modes 0-3, copies),
+# any other tree of the supported functions as one postfix program
+# (pa_vec_eval), and only trees with other functions through the reference's
+# host broadcast on synced parts.
 struct HIPBroadcasted{F,A}
   f::F
   args::A
@@ -697,13 +706,290 @@ function Base.materialize!(y::HIPVector{T}, bc::HIPBroadcasted) where {T<:Device
     mode === :copy && return copyto!(y, x)
     return _axpby!(y, x, a === nothing ? zero(T) : a, mode)
   end
-  # any other expression: the reference's host broadcast (Interfaces.jl:1688-1765)
+  # any other tree of the supported functions: one pass on the device
+  prog = _expr_encode(T, bc)
+  prog === nothing || return _expr_eval!(y, prog, bc)
+  # trees with other functions: the reference's host broadcast (Interfaces.jl:1688-1765)
   host = _host_broadcasted(bc)
   invoke(Base.materialize!, Tuple{PVector,PartitionedArrays.DistributedBroadcasted}, y, host)
 end
 Base.materialize!(y::PVector, bc::HIPBroadcasted) =
   invoke(Base.materialize!, Tuple{PVector,PartitionedArrays.DistributedBroadcasted}, y, _host_broadcasted(bc))
-Base.materialize(bc::HIPBroadcasted) = Base.materialize(_host_broadcasted(bc))
+function Base.materialize(bc::HIPBroadcasted)
+  T = _expr_eltype(bc)
+  prog = T === nothing ? nothing : _expr_encode(T, bc)
+  prog === nothing && return Base.materialize(_host_broadcasted(bc))
+  _expr_eval!(PVector{T}(undef, bc.rows), prog, bc)   # Interfaces.jl:1694-1708
+end
+
+# ---- broadcast expressions as postfix programs (include/pa_hip.h: pa_expr) --
+# The tree's functions map to op codes; every node is tagged with its type as
+# Julia's broadcast infers it (T, or the wide type when an operand is a
+# Float64 / ComplexF64 scalar or a wide node; real valued over complex T for
+# a Float64 scalar, abs2 and comparisons).  Of two sibling subtrees the one
+# that needs more stack slots is emitted first (the reversed operand mode
+# keeps left ∘ right); scalars ride as immediates of their op.  A tree the
+# program cannot hold (other functions, too deep, too long, complex division)
+# encodes to `nothing` and takes the host path.
+const PA_EXPR_MAX_OPS, PA_EXPR_MAX_VECS, PA_EXPR_MAX_SCALARS, PA_EXPR_MAX_DEPTH = 32, 8, 8, 4
+const PA_EXPR_WIDE, PA_EXPR_LREAL, PA_EXPR_RREAL = 0x01, 0x02, 0x04
+const PA_EXPR_SS, PA_EXPR_SC, PA_EXPR_CS, PA_EXPR_RS = 0x00, 0x08, 0x10, 0x18
+const PA_REDUCE_SUM, PA_REDUCE_MAX, PA_REDUCE_MIN = Cint(0), Cint(1), Cint(2)
+struct PaExprOp
+  code::UInt8
+  arg::UInt8
+  flags::UInt8
+  pad::UInt8
+end
+struct PaExpr
+  nops::Int32
+  ops::NTuple{32,PaExprOp}
+end
+mutable struct ExprEncoder
+  vecs::Vector{Any}          # distinct HIPVector operands
+  scal::Vector{UInt8}        # 16-byte scalar slots
+  kinds::Vector{Cint}        # 0 element type, 1 Float64, 2 ComplexF64, 3 real(T)
+  ops::Vector{PaExprOp}
+  sp::Int
+  depth::Int
+end
+
+function _binary_code(f)
+  f === (+) && return 2
+  f === (-) && return 3
+  f === (*) && return 4
+  f === (/) && return 5
+  f === (<) && return 10
+  f === (<=) && return 11
+  f === (>) && return 12
+  f === (>=) && return 13
+  f === (==) && return 14
+  f === (!=) && return 15
+  -1
+end
+function _unary_code(f)
+  (f === identity || f === (+)) && return 0   # no op
+  f === (-) && return 6
+  f === abs && return 7
+  f === abs2 && return 8
+  f === conj && return 9
+  -1
+end
+
+# scalar kind as _bcast_scalar types it
+# (3: a value of real(T) next to complex vectors, Julia's Real ∘ Complex methods)
+_expr_kind(::Type{T}, a::Float64) where {T} = 1
+_expr_kind(::Type{T}, a::Float64) where {T<:Complex} = 1
+_expr_kind(::Type{T}, a::ComplexF64) where {T<:Complex} = 2
+_expr_kind(::Type{T}, a::Real) where {T<:Complex} = 3
+_expr_kind(::Type{T}, a) where {T} = 0
+
+# (wide, real valued) of an operand, or nothing when the tree is not supported
+_expr_type(::Type{T}, a::HIPVector{T}) where {T} = (false, !(T <: Complex))
+_expr_type(::Type{T}, a::HIPVector) where {T} = nothing   # mixed element types
+function _expr_type(::Type{T}, a::Number) where {T}
+  k = _expr_kind(T, a)
+  k == 0 && T <: Real && !(a isa Real) && return nothing   # host path raises the InexactError
+  (k == 1 || k == 2, !(T <: Complex) || k == 1 || k == 3)
+end
+function _expr_type(::Type{T}, b::HIPBroadcasted) where {T}
+  ts = map(a -> _expr_type(T, a), b.args)
+  any(t -> t === nothing, ts) && return nothing
+  wide = any(t -> t[1], ts)
+  allreal = all(t -> t[2], ts)
+  if length(b.args) == 1
+    c = _unary_code(b.f)
+    (c < 0 || (c == 7 && !allreal)) && return nothing
+    return (wide, allreal || c == 8)
+  end
+  length(b.args) == 2 || return nothing
+  c = _binary_code(b.f)
+  c < 0 && return nothing
+  (c == 5 || 10 <= c <= 13) && !allreal && return nothing   # complex division, ordered comparison
+  (wide && c < 10, allreal || c >= 10)   # a comparison's Bool takes the other operand's type
+end
+
+_expr_need(a::HIPVector) = 1
+_expr_need(a::Number) = 0
+function _expr_need(b::HIPBroadcasted)
+  n = map(_expr_need, b.args)
+  (length(n) == 1 || 0 in n) && return max(maximum(n), 1)
+  n[1] >= n[2] ? max(n[1], n[2] + 1) : max(n[2], n[1] + 1)
+end
+
+function _expr_tags(::Type{T}, a) where {T}
+  t = _expr_type(T, a)
+  (t[1] ? PA_EXPR_WIDE : 0x00) | ((T <: Complex && t[2]) ? PA_EXPR_LREAL : 0x00)
+end
+
+function _expr_scalar!(e::ExprEncoder, ::Type{T}, a) where {T}
+  k = _expr_kind(T, a)
+  v = k == 0 ? T(a) : k == 3 ? real(T)(a) : a
+  slot = zeros(UInt8, 16)
+  GC.@preserve slot unsafe_store!(convert(Ptr{typeof(v)}, pointer(slot)), v)
+  for j in eachindex(e.kinds)
+    e.kinds[j] == k && e.scal[16j-15:16j] == slot && return UInt8(j - 1)
+  end
+  append!(e.scal, slot)
+  push!(e.kinds, Cint(k))
+  UInt8(length(e.kinds) - 1)
+end
+
+function _expr_push!(e::ExprEncoder, op::PaExprOp)
+  push!(e.ops, op)
+  e.sp += 1
+  e.depth = max(e.depth, e.sp)
+end
+
+function _expr_emit!(e::ExprEncoder, ::Type{T}, a::HIPVector) where {T}
+  k = findfirst(v -> v === a, e.vecs)
+  if k === nothing
+    push!(e.vecs, a)
+    k = length(e.vecs)
+  end
+  _expr_push!(e, PaExprOp(0x00, UInt8(k - 1), 0x00, 0x00))
+end
+_expr_emit!(e::ExprEncoder, ::Type{T}, a::Number) where {T} =
+  _expr_push!(e, PaExprOp(0x01, _expr_scalar!(e, T, a), _expr_tags(T, a), 0x00))
+function _expr_emit!(e::ExprEncoder, ::Type{T}, b::HIPBroadcasted) where {T}
+  if length(b.args) == 1
+    _expr_emit!(e, T, b.args[1])
+    c = _unary_code(b.f)
+    c == 0 || push!(e.ops, PaExprOp(UInt8(c), 0x00, _expr_tags(T, b.args[1]), 0x00))
+    return
+  end
+  l, r = b.args
+  tl, tr = _expr_tags(T, l), _expr_tags(T, r)
+  fl = ((tl | tr) & PA_EXPR_WIDE) | (tl & PA_EXPR_LREAL) | ((tr & PA_EXPR_LREAL) != 0 ? PA_EXPR_RREAL : 0x00)
+  c = UInt8(_binary_code(b.f))
+  if r isa Number
+    _expr_emit!(e, T, l)
+    push!(e.ops, PaExprOp(c, _expr_scalar!(e, T, r), fl | PA_EXPR_SC, 0x00))
+  elseif l isa Number
+    _expr_emit!(e, T, r)
+    push!(e.ops, PaExprOp(c, _expr_scalar!(e, T, l), fl | PA_EXPR_CS, 0x00))
+  else
+    first_left = _expr_need(l) >= _expr_need(r)
+    _expr_emit!(e, T, first_left ? l : r)
+    _expr_emit!(e, T, first_left ? r : l)
+    e.sp -= 1
+    push!(e.ops, PaExprOp(c, 0x00, fl | (first_left ? PA_EXPR_SS : PA_EXPR_RS), 0x00))
+  end
+  nothing
+end
+
+# (PaExpr, encoder, root is real valued) or nothing
+function _expr_encode(::Type{T}, root::HIPArg) where {T<:DeviceEltype}
+  t = _expr_type(T, root)
+  t === nothing && return nothing
+  e = ExprEncoder(Any[], UInt8[], Cint[], PaExprOp[], 0, 0)
+  _expr_emit!(e, T, root)
+  (length(e.ops) > PA_EXPR_MAX_OPS || e.depth > PA_EXPR_MAX_DEPTH || length(e.vecs) > PA_EXPR_MAX_VECS ||
+   length(e.kinds) > PA_EXPR_MAX_SCALARS) && return nothing
+  nul = PaExprOp(0x00, 0x00, 0x00, 0x00)
+  ops = ntuple(i -> i <= length(e.ops) ? e.ops[i] : nul, 32)
+  (PaExpr(Int32(length(e.ops)), ops), e, t[2])
+end
+
+_expr_eltype(a::HIPVector{T}) where {T<:DeviceEltype} = T
+_expr_eltype(a) = nothing
+function _expr_eltype(b::HIPBroadcasted)
+  for a in b.args
+    T = _expr_eltype(a)
+    T === nothing || return T
+  end
+  nothing
+end
+
+# ghosts are computed only when every vector operand shares one rows object (Interfaces.jl:1730)
+_expr_shared(a, rows) = true
+_expr_shared(a::HIPVector, rows) = a.rows === rows
+_expr_shared(b::HIPBroadcasted, rows) = all(a -> _expr_shared(a, rows), b.args)
+
+function _expr_eval!(y::HIPVector{T}, prog, bc::HIPArg) where {T<:DeviceEltype}
+  expr, e, _ = prog
+  all_lids = _expr_shared(bc, y.rows)
+  all_lids || @assert all(v -> oids_are_equal(y.rows, v.rows), e.vecs)
+  aliased = any(v -> v === y, e.vecs)
+  vh = map(dev_vec, e.vecs)
+  ih = map(v -> dev_idx(v.rows), e.vecs)
+  yv = (all_lids && !aliased) ? dev_vec_nocopy(y) : dev_vec(y)   # owned only: y's ghosts are kept
+  iy = dev_idx(y.rows)
+  ns = length(e.kinds)
+  for i in eachindex(yv)
+    vi = Ptr{Cvoid}[h[i] for h in vh]
+    ii = Ptr{Cvoid}[h[i] for h in ih]
+    check(ccall((:pa_vec_eval, libpa), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ref{PaExpr}, Cint, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Cint, Ptr{UInt8},
+                 Ptr{Cint}, Cint),
+                yv[i], iy[i], Ref(expr), Cint(length(vi)), vi, ii, Cint(ns), e.scal, e.kinds, all_lids ? 1 : 0))
+  end
+  mark_device_newer!(y)
+end
+
+# the tree reduced over the owned values (kind PA_REDUCE_*), or nothing when
+# it is not supported; SUM: a T, MAX / MIN: a Float64
+function _expr_reduce(::Type{T}, kind::Cint, bc::HIPArg) where {T<:DeviceEltype}
+  prog = _expr_encode(T, bc)
+  prog === nothing && return nothing
+  expr, e, isreal = prog
+  (kind == PA_REDUCE_SUM || isreal) || return nothing
+  vh = map(dev_vec, e.vecs)
+  ih = map(v -> dev_idx(v.rows), e.vecs)
+  n = length(vh[1])
+  vflat = Ptr{Cvoid}[h[i] for i in 1:n for h in vh]
+  iflat = Ptr{Cvoid}[h[i] for i in 1:n for h in ih]
+  r = Ref{ComplexF64}(0)   # 16 bytes: a T (SUM) or a Float64 (MAX / MIN) at offset 0
+  check(ccall((:pa_reduce_expr_all, libpa), Cint,
+              (Cint, Cint, Ref{PaExpr}, Cint, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Cint, Ptr{UInt8}, Ptr{Cint},
+               Ref{ComplexF64}),
+              n, kind, Ref(expr), Cint(length(e.vecs)), vflat, iflat, Cint(length(e.kinds)), e.scal, e.kinds, r))
+  S = kind == PA_REDUCE_SUM ? T : Float64
+  v = GC.@preserve r unsafe_load(convert(Ptr{S}, Base.unsafe_convert(Ptr{ComplexF64}, r)))
+  (kind == PA_REDUCE_SUM && isreal) ? real(v) : v
+end
+
+_expr_node(f, args...) = HIPBroadcasted(f, args, _rows(first(a for a in args if a isa HIPArg)))
+
+# sum of a tree (Interfaces.jl:1973-1983 over the broadcast's values)
+function Base.sum(bc::HIPBroadcasted)
+  T = _expr_eltype(bc)
+  r = T === nothing ? nothing : _expr_reduce(T, PA_REDUCE_SUM, bc)
+  r === nothing ? sum(Base.materialize(bc)) : r
+end
+
+# == (Interfaces.jl:1682-1686): equal lengths, parts and owned values
+function Base.:(==)(a::HIPVector{T}, b::HIPVector{T}) where {T<:DeviceEltype}
+  length(a) == length(b) && num_parts(a.values) == num_parts(b.values) || return false
+  map(num_oids, a.rows.partition.parts) == map(num_oids, b.rows.partition.parts) || return false
+  _expr_reduce(T, PA_REDUCE_MIN, _expr_node(==, a, b)) > 0
+end
+
+# maximum / minimum, plain and mapped with abs / abs2 / identity
+# (Interfaces.jl:1841-1863); any(f, v) / all(f, v) with a closure stay generic
+const HIPMapped = Union{typeof(abs),typeof(abs2),typeof(identity)}
+function _expr_extremum(f, a::HIPVector{T}, kind::Cint) where {T<:DeviceEltype}
+  r = _expr_reduce(T, kind, _expr_node(f, a))
+  r === nothing ? nothing : real(T)(r)
+end
+function Base.maximum(f::HIPMapped, a::HIPVector{T}) where {T<:DeviceEltype}
+  r = _expr_extremum(f, a, PA_REDUCE_MAX)
+  r === nothing ? invoke(maximum, Tuple{Function,PVector}, f, a) : r
+end
+function Base.minimum(f::HIPMapped, a::HIPVector{T}) where {T<:DeviceEltype}
+  r = _expr_extremum(f, a, PA_REDUCE_MIN)
+  r === nothing ? invoke(minimum, Tuple{Function,PVector}, f, a) : r
+end
+Base.maximum(a::HIPVector{T}) where {T<:Union{Float32,Float64}} = maximum(identity, a)
+Base.minimum(a::HIPVector{T}) where {T<:Union{Float32,Float64}} = minimum(identity, a)
+
+# Distances (Interfaces.jl:1774-1817): Σ |a - b|² in one pass
+function (d::Distances.SqEuclidean)(a::HIPVector{T}, b::HIPVector{T}) where {T<:DeviceEltype}
+  @assert oids_are_equal(a.rows, b.rows)
+  real(sum(_expr_node(abs2, _expr_node(-, a, b))))
+end
+(d::Distances.Euclidean)(a::HIPVector{T}, b::HIPVector{T}) where {T<:DeviceEltype} =
+  sqrt(Distances.SqEuclidean()(a, b))
 
 _host_arg(a) = a
 _host_arg(a::HIPBroadcasted) = _host_broadcasted(a)

@@ -21,5 +21,7 @@ from .device import DeviceMatrix, HIPBackend, HIPDistributedBackend, device_inde
 from .pvector import (COO, CSC, CSR, PSparseMatrix, PVector, assemble_, axmy_, axpy_, cg_, cg_update_,  # noqa: F401
                       compresscoo, copyto_, csr_init, sparsecsr, fillstored_, dot, exchange_, matvec, mul_, mul_dot_, norm, psum, rmul_,
                       sub_, xpby_)
+from .pvector import (Broadcasted, ExprProgram, abs2, all_, any_, assign_, conj, encode_expr, eq, euclidean,  # noqa: F401
+                      isequal, materialize, maximum, minimum, ne, sqeuclidean)
 from .ptimers import PTimer  # noqa: F401
 from . import drivers  # noqa: F401

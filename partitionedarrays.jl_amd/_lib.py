@@ -20,6 +20,23 @@ PA_REPLACE, PA_ADD = 0, 1
 TUNE_DROP = -(2 ** 31)  # pa_ctx_tune: drop a context's override (PA_TUNE_DROP)
 PA_BCAST_F64, PA_BCAST_C128 = 8, 16  # pa_vec_axpby scalar kinds (Float64 / ComplexF64 scalars)
 
+# broadcast expressions (pa_expr of include/pa_hip.h)
+EXPR_MAX_OPS, EXPR_MAX_VECS, EXPR_MAX_SCALARS, EXPR_MAX_DEPTH = 32, 8, 8, 4
+(OP_VEC, OP_SCAL, OP_ADD, OP_SUB, OP_MUL, OP_DIV, OP_NEG, OP_ABS, OP_ABS2, OP_CONJ,
+ OP_LT, OP_LE, OP_GT, OP_GE, OP_EQ, OP_NE) = range(16)
+EXPR_WIDE, EXPR_LREAL, EXPR_RREAL = 1, 2, 4
+EXPR_SS, EXPR_SC, EXPR_CS, EXPR_RS = 0, 8, 16, 24  # operand modes of a binary op
+REDUCE_SUM, REDUCE_MAX, REDUCE_MIN = 0, 1, 2
+
+
+class ExprOp(C.Structure):
+    _fields_ = [("code", C.c_uint8), ("arg", C.c_uint8), ("flags", C.c_uint8), ("pad", C.c_uint8)]
+
+
+class Expr(C.Structure):
+    _fields_ = [("nops", C.c_int32), ("ops", ExprOp * EXPR_MAX_OPS)]
+
+
 DTYPES = {
     np.dtype(np.float32): PA_F32,
     np.dtype(np.float64): PA_F64,
@@ -68,6 +85,10 @@ _SIGS = {
     "pa_vec_fill": [_p, _p],
     "pa_vec_copy": [_p, _p, _p, _p, C.c_int],
     "pa_vec_axpby": [_p, _p, _p, _p, C.c_int, C.c_int],
+    "pa_expr_check": [_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "pa_vec_eval": [_p, _p, _p, C.c_int, C.POINTER(_p), C.POINTER(_p), C.c_int, _p, C.POINTER(C.c_int), C.c_int],
+    "pa_reduce_expr_all": [C.c_int, C.c_int, _p, C.c_int, C.POINTER(_p), C.POINTER(_p), C.c_int, _p,
+                           C.POINTER(C.c_int), _p],
     "pa_mat_from_csc": [_p, C.c_int, C.c_int, C.c_int64, C.c_int64, _p, _p, _p, _p, _p, C.POINTER(_p)],
     "pa_mat_from_csr": [_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, _p, _p, _p, _p, _p, C.POINTER(_p)],
     "pa_coo_create": [_p, C.c_int, C.c_int64, _i64p, _i64p, _p, C.POINTER(_p)],

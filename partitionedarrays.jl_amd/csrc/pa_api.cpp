@@ -4496,6 +4496,215 @@ int pa_sum_all(int n, const pa_vec* const a[], const pa_index* const ia[], void*
 }
 
 // ---------------------------------------------------------------------------
+// Broadcast expressions (Interfaces.jl:1688-1765): the program checks, then
+// one launch per part (pa_expr.hip).
+namespace {
+
+// What pa_expr_check infers while it replays the program on a stack of node
+// types: PA_EXPR_WIDE (the node is of wide_of<T>) and, for complex T,
+// PA_EXPR_LREAL (the node is real valued).
+int expr_check(const pa_expr* prog, int dtype, int nvec, int nscal, const int* scalar_kinds, int* depth_out,
+               int* result_flags) {
+  CHECK_ARG(prog, "expression: null program");
+  CHECK_ARG(valid_dtype(dtype), "invalid dtype");
+  CHECK_ARG(prog->nops >= 1, "expression: empty program");
+  CHECK_ARG(prog->nops <= PA_EXPR_MAX_OPS, "expression: more than PA_EXPR_MAX_OPS (32) ops");
+  CHECK_ARG(nvec >= 0 && nvec <= PA_EXPR_MAX_VECS, "expression: more than PA_EXPR_MAX_VECS (8) vector operands");
+  CHECK_ARG(nscal >= 0 && nscal <= PA_EXPR_MAX_SCALARS, "expression: more than PA_EXPR_MAX_SCALARS (8) scalars");
+  CHECK_ARG(nscal == 0 || scalar_kinds, "expression: null scalar kinds");
+  const bool cplx = dtype == PA_C64 || dtype == PA_C128;
+  int sflags[PA_EXPR_MAX_SCALARS] = {};
+  for (int k = 0; k < nscal; ++k) {
+    const int sk = scalar_kinds[k];
+    CHECK_ARG(sk >= 0 && sk <= 3,
+              "expression: scalar kind must be 0 (element type), 1 (Float64), 2 (ComplexF64) or 3 (real(T))");
+    CHECK_ARG(sk != 2 || cplx, "expression: a ComplexF64 scalar into a real vector (InexactError)");
+    sflags[k] = (sk == 1 || sk == 2 ? PA_EXPR_WIDE : 0) | ((sk == 1 || sk == 3) && cplx ? PA_EXPR_LREAL : 0);
+  }
+  const int real_bit = PA_EXPR_LREAL;  // a stack entry's "real valued" mark (complex T only)
+  int st[PA_EXPR_MAX_DEPTH];
+  int sp = 0, depth = 0;
+  for (int pc = 0; pc < prog->nops; ++pc) {
+    const pa_expr_op& op = prog->ops[pc];
+    const int mode = op.flags & PA_EXPR_MODE;
+    CHECK_ARG(op.code <= PA_OP_NE, "expression: unsupported op code");
+    CHECK_ARG((op.flags & ~(PA_EXPR_WIDE | PA_EXPR_LREAL | PA_EXPR_RREAL | PA_EXPR_MODE)) == 0 && op.pad == 0,
+              "expression: unknown op flags");
+    int want;  // the tags this op must carry
+    if (op.code == PA_OP_VEC || op.code == PA_OP_SCAL) {
+      CHECK_ARG(mode == 0, "expression: a push takes no operand mode");
+      if (op.code == PA_OP_VEC) CHECK_ARG(op.arg < nvec, "expression: vector operand number out of range");
+      else CHECK_ARG(op.arg < nscal, "expression: scalar number out of range");
+      CHECK_ARG(sp < PA_EXPR_MAX_DEPTH, "expression: deeper than PA_EXPR_MAX_DEPTH (4) stack slots");
+      want = op.code == PA_OP_VEC ? 0 : sflags[op.arg];
+      st[sp++] = want;
+    } else if (op.code >= PA_OP_NEG && op.code <= PA_OP_CONJ) {
+      CHECK_ARG(mode == 0, "expression: a unary op takes no operand mode");
+      CHECK_ARG(sp >= 1, "expression: stack underflow");
+      const int a = st[sp - 1];
+      CHECK_ARG(op.code != PA_OP_ABS || !cplx || (a & real_bit), "expression: abs of a complex value is not supported");
+      want = a;
+      if (cplx && (op.code == PA_OP_ABS2 || op.code == PA_OP_ABS)) st[sp - 1] = a | real_bit;
+    } else {
+      int l, r;  // node types of the left and right operand
+      if (mode == PA_EXPR_SS || mode == PA_EXPR_RS) {
+        CHECK_ARG(sp >= 2, "expression: stack underflow");
+        l = mode == PA_EXPR_SS ? st[sp - 2] : st[sp - 1];
+        r = mode == PA_EXPR_SS ? st[sp - 1] : st[sp - 2];
+        --sp;
+      } else {
+        CHECK_ARG(sp >= 1, "expression: stack underflow");
+        CHECK_ARG(op.arg < nscal, "expression: scalar number out of range");
+        l = mode == PA_EXPR_SC ? st[sp - 1] : sflags[op.arg];
+        r = mode == PA_EXPR_SC ? sflags[op.arg] : st[sp - 1];
+      }
+      const bool lreal = !cplx || (l & real_bit), rreal = !cplx || (r & real_bit);
+      const bool ordered = op.code >= PA_OP_LT && op.code <= PA_OP_GE;
+      CHECK_ARG(op.code != PA_OP_DIV || (lreal && rreal), "expression: complex division is not supported");
+      CHECK_ARG(!ordered || (lreal && rreal), "expression: ordered comparison of complex values");
+      want = ((l | r) & PA_EXPR_WIDE) | (cplx && lreal ? PA_EXPR_LREAL : 0) | (cplx && rreal ? PA_EXPR_RREAL : 0);
+      // a comparison's 1 / 0 is of T (Julia's Bool takes the other operand's type in arithmetic)
+      const bool cmp = op.code >= PA_OP_LT;
+      const bool res_real = cplx && ((lreal && rreal) || cmp);
+      st[sp - 1] = (cmp ? 0 : want & PA_EXPR_WIDE) | (res_real ? real_bit : 0);
+    }
+    CHECK_ARG((op.flags & ~PA_EXPR_MODE) == want, "expression: an op's type tags differ from the inferred node type");
+    if (sp > depth) depth = sp;
+  }
+  CHECK_ARG(sp == 1, "expression: the program must leave one value");
+  if (depth_out) *depth_out = depth;
+  if (result_flags) *result_flags = st[0];
+  return 0;
+}
+
+// the kernel argument of one part: operands addressed over all lids, or over
+// the owned values through each operand's own index set; *fast = every
+// address is the identity (16 B steps), *n = elements
+int expr_args(const pa_expr* prog, int dtype, pa_ctx* ctx, int nvec, const pa_vec* const v[],
+              const pa_index* const v_idx[], int nscal, const void* scalars, const int* scalar_kinds, bool all_lids,
+              int64_t n_y, ExprArgs* a, bool* fast, int64_t* n) {
+  CHECK_ARG(nvec == 0 || v, "expression: null operands");
+  CHECK_ARG(all_lids || nvec == 0 || v_idx, "expression over owned values needs the operands' index sets");
+  CHECK_ARG(nscal == 0 || scalars, "expression: null scalars");
+  std::memset(a, 0, sizeof(*a));
+  a->prog = *prog;
+  a->nvec = nvec;
+  for (int k = 0; k < nvec; ++k) {
+    CHECK_ARG(v[k], "expression: null operand");
+    CHECK_ARG(v[k]->dtype == dtype, "expression: operands of different element types");
+    CHECK_ARG(v[k]->ctx == ctx, "expression: vectors of different parts");
+    a->v[k] = v[k]->d;
+    if (all_lids) {
+      CHECK_ARG(*n < 0 || v[k]->n == *n, "expression over all lids: lengths differ");
+      *n = v[k]->n;
+    } else {
+      CHECK_ARG(v_idx[k] && v_idx[k]->nlids == v[k]->n, "expression: index set does not describe the operand");
+      CHECK_ARG(*n < 0 || v_idx[k]->noids == *n, "expression: owned counts differ (oids_are_equal)");
+      *n = v_idx[k]->noids;
+      a->map[k] = v_idx[k]->d_oid_to_lid;
+      if (a->map[k]) *fast = false;
+    }
+  }
+  if (*n < 0) *n = n_y;
+  for (int k = 0; k < nscal; ++k) {
+    const char* s = (const char*)scalars + 16 * k;
+    if (scalar_kinds[k] == 2) a->scal[k] = *(const c128*)s;
+    else if (scalar_kinds[k] == 1) a->scal[k] = c128{*(const double*)s, 0.0};
+    else if (scalar_kinds[k] == 3 && dtype == PA_C64) a->scal[k] = c128{(double)*(const float*)s, 0.0};
+    else if (scalar_kinds[k] == 3 && dtype == PA_C128) a->scal[k] = c128{*(const double*)s, 0.0};
+    else if (dtype == PA_F32) a->scal[k] = c128{(double)*(const float*)s, 0.0};
+    else if (dtype == PA_F64) a->scal[k] = c128{*(const double*)s, 0.0};
+    else if (dtype == PA_C64) a->scal[k] = c128{(double)((const float*)s)[0], (double)((const float*)s)[1]};
+    else a->scal[k] = *(const c128*)s;
+  }
+  return 0;
+}
+
+// NaN wins; of equal values max picks +0.0 and min -0.0 (Julia's max / min)
+double fold_minmax(int kind, double a, double b) {
+  if (a != a) return a;
+  if (b != b) return b;
+  if (kind == PA_REDUCE_MAX) return a > b ? a : b > a ? b : (std::signbit(a) ? b : a);
+  return a < b ? a : b < a ? b : (std::signbit(a) ? a : b);
+}
+
+}  // namespace
+
+int pa_expr_check(const pa_expr* prog, int dtype, int nvec, int nscal, const int* scalar_kinds, int* depth,
+                  int* result_flags) {
+  return expr_check(prog, dtype, nvec, nscal, scalar_kinds, depth, result_flags);
+}
+
+int pa_vec_eval(pa_vec* y, const pa_index* y_idx, const pa_expr* prog, int nvec, const pa_vec* const v[],
+                const pa_index* const v_idx[], int nscal, const void* scalars, const int* scalar_kinds,
+                int all_lids) {
+  CHECK_ARG(y, "null argument");
+  if (expr_check(prog, y->dtype, nvec, nscal, scalar_kinds, nullptr, nullptr)) return -1;
+  ExprArgs a;
+  bool fast = true;
+  int64_t n = -1;
+  const int32_t* ymap = nullptr;
+  if (all_lids) {
+    n = y->n;
+  } else {
+    CHECK_ARG(y_idx && y_idx->nlids == y->n, "expression over owned values needs y's index set");
+    n = y_idx->noids;
+    ymap = y_idx->d_oid_to_lid;
+    if (ymap) fast = false;
+  }
+  if (expr_args(prog, y->dtype, y->ctx, nvec, v, v_idx, nscal, scalars, scalar_kinds, all_lids != 0, n, &a, &fast,
+                &n))
+    return -1;
+  HIPC(hipSetDevice(y->ctx->device));
+  launch_expr_store(y->dtype, n, a, y->d, ymap, fast, y->ctx->s_main);
+  HIPC(hipGetLastError());
+  return 0;
+}
+
+int pa_reduce_expr_all(int n, int kind, const pa_expr* prog, int nvec, const pa_vec* const v[],
+                       const pa_index* const v_idx[], int nscal, const void* scalars, const int* scalar_kinds,
+                       void* result) {
+  CHECK_ARG(n >= 1 && v && v_idx && result, "null argument");
+  CHECK_ARG(kind == PA_REDUCE_SUM || kind == PA_REDUCE_MAX || kind == PA_REDUCE_MIN, "invalid reduction kind");
+  CHECK_ARG(nvec >= 1 && nvec <= PA_EXPR_MAX_VECS && v[0], "reduction of an expression: 1 to 8 vector operands");
+  const int dt = v[0]->dtype;
+  const bool cplx = dt == PA_C64 || dt == PA_C128;
+  int rflags = 0;
+  if (expr_check(prog, dt, nvec, nscal, scalar_kinds, nullptr, &rflags)) return -1;
+  CHECK_ARG(kind == PA_REDUCE_SUM || !cplx || (rflags & PA_EXPR_LREAL),
+            "maximum / minimum of a complex-valued expression");
+  std::vector<ExprArgs> args(n);
+  std::vector<int64_t> len(n, -1);
+  std::vector<char> fast(n, 1);
+  std::vector<pa_ctx*> ctxs(n);
+  for (int i = 0; i < n; ++i) {  // every part's arguments are checked before the first launch
+    CHECK_ARG(v[(size_t)i * nvec], "expression: null operand");
+    ctxs[i] = v[(size_t)i * nvec]->ctx;
+    bool f = true;
+    if (expr_args(prog, dt, ctxs[i], nvec, v + (size_t)i * nvec, v_idx + (size_t)i * nvec, nscal, scalars,
+                  scalar_kinds, false, 0, &args[i], &f, &len[i]))
+      return -1;
+    fast[i] = f;
+  }
+  for (int i = 0; i < n; ++i) {
+    pa_ctx* c = ctxs[i];
+    HIPC(hipSetDevice(c->device));
+    launch_expr_reduce(dt, kind, len[i], args[i], fast[i] != 0, c->d_partials, c->d_result, c->d_ticket, c->s_main);
+  }
+  HIPC(hipGetLastError());
+  std::vector<c128> vals;
+  if (gather_results(n, ctxs.data(), kind == PA_REDUCE_SUM && cplx, &vals)) return -1;
+  if (kind == PA_REDUCE_SUM) {
+    store_scalar(dt, fold_parts(dt, vals, false), result);
+  } else {  // reduce(max, partials, init=typemin) in part order (Interfaces.jl:1843, 1855)
+    double r = kind == PA_REDUCE_MAX ? -HUGE_VAL : HUGE_VAL;
+    for (const auto& p : vals) r = fold_minmax(kind, r, p.re);
+    *(double*)result = r;
+  }
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
 // Synthetic Cartesian stencil operator of one part box, built on the device
 // (benchmark driver; equals pa_mat_from_csc of the CSC the oracle's drivers
 // assemble, see tests/test_gpu_parity.py).

@@ -279,6 +279,24 @@ struct PullGroup {
   void* v[PA_GROUP_MAX];
 };
 
+// One part's share of a broadcast expression (pa_vec_eval /
+// pa_reduce_expr_all), passed to the kernels of pa_expr.hip by value: the
+// program and the operand numbers are wave-uniform, so the interpreter's
+// branches are scalar branches.
+struct ExprArgs {
+  pa_expr prog;
+  int nvec;
+  const void* v[PA_EXPR_MAX_VECS];
+  const int32_t* map[PA_EXPR_MAX_VECS];  // element i of operand k is v[k][map[k][i]] (null: i)
+  c128 scal[PA_EXPR_MAX_SCALARS];        // widened (exactly); a real scalar has im = 0
+};
+// y[ymap[i]] = prog(i) for i < n; fast: every map is null (16 B per lane and operand)
+void launch_expr_store(int dtype, int64_t n, const ExprArgs& a, void* y, const int32_t* ymap, bool fast,
+                       hipStream_t st);
+// kind PA_REDUCE_*: the part's value (double / c128 accumulator) into result[0]
+void launch_expr_reduce(int dtype, int kind, int64_t n, const ExprArgs& a, bool fast, void* partials,
+                        void* result, unsigned* ticket, hipStream_t st);
+
 // Cartesian part box of a synthetic stencil operator (pa_mat_stencil).
 struct StencilGeom {
   int64_t N[3];   // global nodes per dim

@@ -107,7 +107,58 @@ class csr_init:
 # ---------------------------------------------------------------------------
 # PVector
 
-class PVector:
+class _ExprOps:
+    """The operators that build a lazy Broadcasted node (Julia's dotted
+    operators on PVectors, Interfaces.jl:1722-1765); shared by PVector and
+    Broadcasted.  No __eq__ / __ne__: identity and hashing stay the
+    default (use eq / ne / isequal)."""
+
+    __array_ufunc__ = None  # numpy scalars on the left defer to __radd__ etc.
+
+    def __add__(self, o):
+        return _node("add", self, o)
+
+    def __radd__(self, o):
+        return _node("add", o, self)
+
+    def __sub__(self, o):
+        return _node("sub", self, o)
+
+    def __rsub__(self, o):
+        return _node("sub", o, self)
+
+    def __mul__(self, o):
+        return _node("mul", self, o)
+
+    def __rmul__(self, o):
+        return _node("mul", o, self)
+
+    def __truediv__(self, o):
+        return _node("div", self, o)
+
+    def __rtruediv__(self, o):
+        return _node("div", o, self)
+
+    def __neg__(self):
+        return _node("neg", self)
+
+    def __abs__(self):
+        return _node("abs", self)
+
+    def __lt__(self, o):
+        return _node("lt", self, o)
+
+    def __le__(self, o):
+        return _node("le", self, o)
+
+    def __gt__(self, o):
+        return _node("gt", self, o)
+
+    def __ge__(self, o):
+        return _node("ge", self, o)
+
+
+class PVector(_ExprOps):
     """PVector{T}(values, rows) (Interfaces.jl:1576-1587): values = PData of
     DeviceVector (num_lids(rows) entries per part)."""
 
@@ -332,21 +383,357 @@ def dot(a: PVector, b: PVector):
 
 
 def norm(a: PVector, p=2):
-    """norm(a, 2) (Interfaces.jl:1767-1772)"""
+    """norm(a, p) (Interfaces.jl:1767-1772): p = 2 (pa_norm2_all), and for
+    real vectors p = 1 as sum(abs.(a)) and p = Inf as maximum(abs.(a))"""
+    if p == 1 or p == math.inf:
+        if np.dtype(a.dtype).kind == "c":
+            raise NotImplementedError("norm(a, p) on HIP parts: p = 1 and p = Inf for real vectors only")
+        return float(psum(abs(a))) if p == 1 else maximum(abs(a))
     if p != 2:
-        raise NotImplementedError("norm(a, p) on HIP parts: p = 2 only")
+        raise NotImplementedError("norm(a, p) on HIP parts: p = 1, 2 or Inf")
     out = np.zeros(1, dtype=np.float64)
     _lib.call("pa_norm2_all", len(a.values.parts), _hs(a.values.parts), _lib.ptr_array(_idx(a)),
               out.ctypes.data_as(C.c_void_p))
     return float(out[0])
 
 
-def psum(a: PVector):
-    """sum(a) (Interfaces.jl:1981-1983)"""
+def psum(a):
+    """sum(a) (Interfaces.jl:1981-1983); of a Broadcasted: the expression
+    summed over the owned values in one pass (pa_reduce_expr_all)"""
+    if isinstance(a, Broadcasted):
+        return _reduce_expr(a, _lib.REDUCE_SUM)
     out = _scalar_out(a.dtype)
     _lib.call("pa_sum_all", len(a.values.parts), _hs(a.values.parts), _lib.ptr_array(_idx(a)),
               out.ctypes.data_as(C.c_void_p))
     return out[0].item()
+
+
+# ---------------------------------------------------------------------------
+# Broadcast expressions (Interfaces.jl:1688-1765) and mapped reductions
+# (1682-1686, 1767-1863): a lazy tree over PVectors and numbers, encoded into
+# the postfix program of include/pa_hip.h and evaluated in one pass per part.
+
+_BINARY = {"add": _lib.OP_ADD, "sub": _lib.OP_SUB, "mul": _lib.OP_MUL, "div": _lib.OP_DIV, "lt": _lib.OP_LT,
+           "le": _lib.OP_LE, "gt": _lib.OP_GT, "ge": _lib.OP_GE, "eq": _lib.OP_EQ, "ne": _lib.OP_NE}
+_UNARY = {"neg": _lib.OP_NEG, "abs": _lib.OP_ABS, "abs2": _lib.OP_ABS2, "conj": _lib.OP_CONJ}
+_COMPARE = ("lt", "le", "gt", "ge", "eq", "ne")
+_NUMBER = (int, float, complex, np.number)
+
+
+def _expr_scalar(a, dtype):
+    """(value, kind) of a scalar operand: kind 0 the element type, 1 Float64,
+    2 ComplexF64 (_scalar_kind's rule); over complex vectors a real scalar of
+    the element type's width (an int, a Float32 next to ComplexF32) is kind 3,
+    a value of real(T), so that Julia's Real ∘ Complex methods apply"""
+    cplx = np.dtype(dtype).kind == "c"
+    if not cplx and np.iscomplexobj(a) and complex(a).imag != 0:
+        raise TypeError("broadcast: a complex scalar into a real vector (InexactError)")
+    v, k = _scalar_kind(a, dtype)
+    if k == 0 and cplx and not np.iscomplexobj(a):
+        return np.zeros(1, dtype).real.dtype.type(a), 3
+    if k == 0:
+        v = np.dtype(dtype).type(complex(a).real if (np.iscomplexobj(a) and not cplx) else a)
+    return v, k >> 3
+
+
+class Broadcasted(_ExprOps):
+    """A lazy broadcast node (DistributedBroadcasted, Interfaces.jl:1688-1692):
+    `op` over PVector / Broadcasted / number operands.  `rows` is the first
+    vector operand's PRange; `ghosts` says whether ghost values are computed
+    too — only when every PVector operand shares one rows object (1730).
+    `wide` / `real`: the node is of the wide type (an operand is a Float64 /
+    ComplexF64 scalar or a wide node) / real valued over complex vectors."""
+
+    def __init__(self, op, *args, check=True):
+        if op not in _BINARY and op not in _UNARY and op != "identity":
+            raise TypeError(f"broadcast: unsupported function {op}")
+        if len(args) != (2 if op in _BINARY else 1):
+            raise TypeError(f"broadcast: {op} takes {2 if op in _BINARY else 1} operand(s)")
+        vecs = [a for a in args if isinstance(a, (PVector, Broadcasted))]
+        if not vecs:
+            raise TypeError("broadcast: no PVector operand")
+        for a in args:
+            if not isinstance(a, (PVector, Broadcasted) + _NUMBER):
+                raise TypeError(f"broadcast: unsupported operand {type(a).__name__}")
+        self.op, self.args = op, args
+        self.rows = vecs[0].rows
+        self.dtype = np.dtype(vecs[0].dtype)
+        for a in vecs[1:]:
+            if np.dtype(a.dtype) != self.dtype:
+                raise TypeError(f"broadcast: mixed element types {self.dtype} and {np.dtype(a.dtype)}")
+            if check and not oids_are_equal(a.rows, self.rows):
+                raise AssertionError("broadcast: owned ids differ")
+        self.ghosts = all(a.rows is self.rows and (a.ghosts if isinstance(a, Broadcasted) else True) for a in vecs)
+        cplx = self.dtype.kind == "c"
+        t = [_operand_type(a, self.dtype) for a in args]  # (wide, real) per operand
+        real = [r or not cplx for _, r in t]
+        # a comparison's 1 / 0 is of the element type (Julia's Bool takes the other operand's type)
+        self.wide = any(w for w, _ in t) and op not in _COMPARE
+        if op in ("div", "abs") and not all(real):
+            raise TypeError(f"broadcast: {op} of complex values is not supported")
+        if op in ("lt", "le", "gt", "ge") and not all(real):
+            raise TypeError("broadcast: ordered comparison of complex values")
+        self.real = cplx and (op in _COMPARE or op in ("abs", "abs2") or all(real))
+
+
+def _operand_type(a, dtype):
+    if isinstance(a, Broadcasted):
+        return a.wide, a.real
+    if isinstance(a, PVector):
+        return False, False
+    k = _expr_scalar(a, dtype)[1]
+    return k in (1, 2), k in (1, 3) and np.dtype(dtype).kind == "c"
+
+
+def _node(op, *args):
+    if not all(isinstance(a, (PVector, Broadcasted) + _NUMBER) for a in args):
+        return NotImplemented
+    return Broadcasted(op, *args)
+
+
+def abs2(a):
+    """abs2.(a)"""
+    return Broadcasted("abs2", a)
+
+
+def conj(a):
+    """conj.(a)"""
+    return Broadcasted("conj", a)
+
+
+def eq(a, b):
+    """a .== b (1 / 0 of the node's type)"""
+    return Broadcasted("eq", a, b)
+
+
+def ne(a, b):
+    """a .!= b"""
+    return Broadcasted("ne", a, b)
+
+
+class ExprProgram:
+    """The encoded form of an expression: `vecs` (the distinct PVector
+    operands), `scalars` ((value, kind) pairs; kinds as pa_hip.h's scalar_kinds), `ops` ((code, arg, flags)
+    triples in postfix order), the stack `depth` it needs and the root's
+    `wide` / `real`."""
+
+    def __init__(self, dtype):
+        self.dtype = np.dtype(dtype)
+        self.vecs, self.scalars, self.ops = [], [], []
+        self.depth = 0
+        self.wide = self.real = False
+
+    def c_args(self):
+        """(pa_expr, nscal, scalar slots, scalar kinds) for the C-ABI"""
+        e = _lib.Expr()
+        e.nops = len(self.ops)
+        for i, (code, arg, flags) in enumerate(self.ops):
+            e.ops[i] = _lib.ExprOp(code, arg, flags, 0)
+        ns = len(self.scalars)
+        buf = bytearray(16 * max(ns, 1))
+        for k, (v, kind) in enumerate(self.scalars):
+            b = np.array([v], dtype=(self.dtype, np.float64, np.complex128, np.asarray(v).dtype)[kind]).tobytes()
+            buf[16 * k:16 * k + len(b)] = b
+        return e, ns, (C.c_char * len(buf)).from_buffer(buf), (C.c_int * max(ns, 1))(*[k for _, k in self.scalars])
+
+
+def encode_expr(root) -> ExprProgram:
+    """Postfix program of a Broadcasted (or a PVector: the identity).  Sibling
+    subtrees are pure, so the one that needs more stack slots is emitted first
+    (the reversed operand mode keeps left ∘ right), which keeps the depth at
+    the tree's minimum; scalars ride as immediates of their binary op."""
+    P = ExprProgram(root.dtype)
+    cplx = P.dtype.kind == "c"
+    need_memo = {}
+
+    def need(a):  # stack slots the subtree needs
+        if isinstance(a, PVector):
+            return 1
+        if not isinstance(a, Broadcasted):
+            return 0
+        if id(a) not in need_memo:
+            n = [need(x) for x in a.args]
+            if len(n) == 1 or 0 in n:
+                need_memo[id(a)] = max(max(n), 1)
+            else:
+                need_memo[id(a)] = max(n[0], n[1] + 1) if n[0] >= n[1] else max(n[1], n[0] + 1)
+        return need_memo[id(a)]
+
+    def scalar(a):
+        v, kind = _expr_scalar(a, P.dtype)
+        key = (kind, np.asarray(v).tobytes())
+        for k, (w, kd) in enumerate(P.scalars):
+            if (kd, np.asarray(w).tobytes()) == key:
+                return k
+        P.scalars.append((v, kind))
+        return len(P.scalars) - 1
+
+    def tags(a):  # PA_EXPR_WIDE | PA_EXPR_LREAL of an operand
+        w, r = _operand_type(a, P.dtype)
+        return (_lib.EXPR_WIDE if w else 0) | (_lib.EXPR_LREAL if (r and cplx) else 0)
+
+    sp = [0]
+
+    def push(code, arg, flags):
+        P.ops.append((code, arg, flags))
+        sp[0] += 1
+        P.depth = max(P.depth, sp[0])
+
+    def emit(a):
+        if isinstance(a, PVector):
+            for k, v in enumerate(P.vecs):
+                if v is a:
+                    break
+            else:
+                P.vecs.append(a)
+                k = len(P.vecs) - 1
+            return push(_lib.OP_VEC, k, 0)
+        if not isinstance(a, Broadcasted):  # a lone scalar
+            return push(_lib.OP_SCAL, scalar(a), tags(a))
+        if a.op == "identity":
+            return emit(a.args[0])
+        if a.op in _UNARY:
+            emit(a.args[0])
+            return P.ops.append((_UNARY[a.op], 0, tags(a.args[0])))
+        l, r = a.args
+        tl, tr = tags(l), tags(r)
+        fl = ((tl | tr) & _lib.EXPR_WIDE) | (tl & _lib.EXPR_LREAL) | (_lib.EXPR_RREAL if tr & _lib.EXPR_LREAL else 0)
+        code = _BINARY[a.op]
+        if not isinstance(r, (PVector, Broadcasted)):
+            emit(l)
+            return P.ops.append((code, scalar(r), fl | _lib.EXPR_SC))
+        if not isinstance(l, (PVector, Broadcasted)):
+            emit(r)
+            return P.ops.append((code, scalar(l), fl | _lib.EXPR_CS))
+        if need(l) >= need(r):
+            emit(l)
+            emit(r)
+            mode = _lib.EXPR_SS
+        else:
+            emit(r)
+            emit(l)
+            mode = _lib.EXPR_RS
+        sp[0] -= 1
+        P.ops.append((code, 0, fl | mode))
+
+    emit(root)
+    if isinstance(root, Broadcasted):
+        P.wide, P.real = root.wide, root.real
+    if len(P.ops) > _lib.EXPR_MAX_OPS:
+        raise TypeError(f"broadcast: the expression needs {len(P.ops)} ops, more than {_lib.EXPR_MAX_OPS}")
+    if P.depth > _lib.EXPR_MAX_DEPTH:
+        raise TypeError(f"broadcast: the expression needs {P.depth} stack slots, more than {_lib.EXPR_MAX_DEPTH}")
+    if len(P.vecs) > _lib.EXPR_MAX_VECS:
+        raise TypeError(f"broadcast: more than {_lib.EXPR_MAX_VECS} vector operands")
+    if len(P.scalars) > _lib.EXPR_MAX_SCALARS:
+        raise TypeError(f"broadcast: more than {_lib.EXPR_MAX_SCALARS} scalars")
+    return P
+
+
+def _as_expr(x):
+    if isinstance(x, Broadcasted):
+        return x
+    if isinstance(x, PVector):
+        return Broadcasted("identity", x)
+    raise TypeError(f"expected a PVector or a broadcast expression, got {type(x).__name__}")
+
+
+def assign_(w: PVector, expr) -> PVector:
+    """w .= expr (materialize!, Interfaces.jl:1710-1720): all lids when every
+    PVector operand and w share one rows object, else the owned values (w's
+    ghosts untouched).  w may be an operand."""
+    expr = _as_expr(expr)
+    if np.dtype(w.dtype) != expr.dtype:
+        raise TypeError(f"broadcast: mixed element types {np.dtype(w.dtype)} and {expr.dtype}")
+    all_lids = 1 if (expr.ghosts and w.rows is expr.rows) else 0
+    if not all_lids and not oids_are_equal(w.rows, expr.rows):
+        raise AssertionError("broadcast: owned ids differ")
+    P = encode_expr(expr)
+    e, ns, sbuf, kinds = P.c_args()
+    iy = _idx(w)
+    iv = [_idx(v) for v in P.vecs]
+    for p, dy in enumerate(w.values.parts):
+        _lib.call("pa_vec_eval", dy.h, iy[p], C.byref(e), len(P.vecs),
+                  _lib.ptr_array([v.values.parts[p].h for v in P.vecs]), _lib.ptr_array([i[p] for i in iv]),
+                  ns, sbuf, kinds, all_lids)
+    return w
+
+
+def materialize(expr) -> PVector:
+    """materialize(bc) (Interfaces.jl:1694-1708): a new PVector on the first
+    operand's rows (ghosts computed when every operand shares them)"""
+    expr = _as_expr(expr)
+    return assign_(PVector.undef(expr.rows, expr.dtype), expr)
+
+
+def _reduce_expr(x, kind):
+    expr = _as_expr(x)
+    P = encode_expr(expr)
+    e, ns, sbuf, kinds = P.c_args()
+    n = len(P.vecs[0].values.parts)
+    iv = [_idx(v) for v in P.vecs]
+    vh = _lib.ptr_array([v.values.parts[p].h for p in range(n) for v in P.vecs])
+    ih = _lib.ptr_array([i[p] for p in range(n) for i in iv])
+    out = np.zeros(1, dtype=P.dtype if kind == _lib.REDUCE_SUM else np.float64)
+    _lib.call("pa_reduce_expr_all", n, kind, C.byref(e), len(P.vecs), vh, ih, ns, sbuf, kinds,
+              out.ctypes.data_as(C.c_void_p))
+    r = out[0].item()
+    return r.real if (isinstance(r, complex) and P.real) else r
+
+
+def _real_valued(x, what):
+    x = _as_expr(x)
+    if x.dtype.kind == "c" and not x.real:
+        raise TypeError(f"{what} of a complex-valued expression")
+    return x
+
+
+def maximum(x) -> float:
+    """maximum(x) / maximum(f, v) as maximum(f(v)) (Interfaces.jl:1841-1851):
+    over the owned values, init -Inf, NaN if any owned element is NaN"""
+    return _reduce_expr(_real_valued(x, "maximum"), _lib.REDUCE_MAX)
+
+
+def minimum(x) -> float:
+    """minimum(x) / minimum(f, v) (Interfaces.jl:1853-1863), init +Inf"""
+    return _reduce_expr(_real_valued(x, "minimum"), _lib.REDUCE_MIN)
+
+
+def _predicate(x, what):
+    if not (isinstance(x, Broadcasted) and x.op in _COMPARE):
+        raise TypeError(f"{what}: expected a comparison (v < c, eq(a, b), ...)")
+    return x
+
+
+def any_(expr) -> bool:
+    """any(f, v) with f a comparison (Interfaces.jl:1827-1832)"""
+    return maximum(_predicate(expr, "any")) > 0
+
+
+def all_(expr) -> bool:
+    """all(f, v) with f a comparison (Interfaces.jl:1834-1839)"""
+    return minimum(_predicate(expr, "all")) > 0
+
+
+def isequal(a: PVector, b: PVector) -> bool:
+    """a == b (Interfaces.jl:1682-1686): equal lengths, parts and owned values"""
+    if len(a) != len(b) or a.values.num_parts != b.values.num_parts:
+        return False
+    if np.dtype(a.dtype) != np.dtype(b.dtype):
+        raise TypeError(f"broadcast: mixed element types {np.dtype(a.dtype)} and {np.dtype(b.dtype)}")
+    if any(s.num_oids != t.num_oids for s, t in zip(a.rows.partition.parts, b.rows.partition.parts)):
+        return False
+    return all_(Broadcasted("eq", a, b, check=False))
+
+
+def sqeuclidean(a: PVector, b: PVector):
+    """Distances.SqEuclidean()(a, b) (Interfaces.jl:1774-1817): Σ |a - b|²"""
+    return psum(abs2(a - b))
+
+
+def euclidean(a: PVector, b: PVector) -> float:
+    """Distances.Euclidean()(a, b): sqrt of sqeuclidean"""
+    return math.sqrt(sqeuclidean(a, b))
 
 
 # ---------------------------------------------------------------------------
