@@ -339,7 +339,8 @@ int finish_sell_layout(pa_mat* A, const std::vector<int32_t>& slen, const std::v
 // The uniform layout of short pattern rows (pa_tune "spmv_uniform", Float64
 // with 2 rows per lane and patterns of at most 7 entries: FD7, C2): the
 // union U of the distinct patterns' offsets (K <= 7 entries, ascending;
-// every pattern is a subsequence of it), and the pattern slices' values
+// every pattern must be a subsequence of it: a matrix with a pattern stored
+// in another column order gets no uniform layout), and the pattern slices' values
 // again at slice s * H * K, entry k of the slice's pattern at U's position
 // e(k) (the others 0, never multiplied).  A wave of the short-row tail
 // launch then knows its values' and x runs' addresses from its slice index
@@ -373,7 +374,11 @@ int build_uniform(pa_mat* A, const std::vector<int32_t>& kind, const std::vector
   for (int64_t p = 0; p < np; ++p)
     for (int32_t k = 0; k < plen[p]; ++k) {
       const int e = (int)(std::lower_bound(U.begin(), U.end(), table[p * K0 + k]) - U.begin());
-      CHECK_ARG(k == 0 || e > emap[p * 8 + k - 1], "uniform layout: a pattern out of column order (internal error)");
+      // a pattern not in ascending column order (a CSR parent's storage
+      // order, e.g. diagonal first): summing its slice in U's order would
+      // change the row's summation order, so the matrix gets no uniform
+      // layout (nothing written yet: desc keeps no emask)
+      if (k > 0 && e <= emap[p * 8 + k - 1]) return 0;
       emap[p * 8 + k] = e;
       emask[p] |= 1 << e;
     }

@@ -1208,10 +1208,16 @@ __global__ __launch_bounds__(256) void k_spmv_sell(SpmvArgs<T> a) {
 
 // One wave of the short-row tail launch over the uniform layout
 // (build_uniform): the slice's values at s * H * K and its x runs at
-// rbase + upat[e] (clamped into x: entries and rows the slice does not hold
-// read some x and are never accumulated) are issued from the slice index
-// and the kernel arguments alone; the descriptor (scalar load) supplies
-// only the row mask and emask, which select the terms.  A lane's R rows are
+// rbase + upat[e] are issued from the slice index and the kernel arguments
+// alone; the descriptor (scalar load) supplies only the row mask and emask,
+// which select the terms.  A run starts at the lane's first row plus the
+// offset wherever one of its R elements lies in x, i.e. in [-(R-1), nx-1]:
+// a regular row's columns are all inside x, so it reads x[row + upat[e]]
+// also when its lane partner's element falls before x[0] or after x[nx-1]
+// (those bytes are the vector's padding, ld_xrun).  Only a run wholly
+// outside x, which no accumulated term uses, is moved to that interval's
+// nearer end (shifting a run that straddles an end of x would hand the
+// valid row its neighbour's x).  A lane's R rows are
 // blocked, as in rows_pattern with 16 B x runs; the terms of a row and
 // their order are rows_pattern's (U's order restricted to the slice's
 // pattern = the pattern's own order).
@@ -1230,12 +1236,12 @@ __device__ __forceinline__ void spmv_wave_u(const SpmvArgs<T>& a, const int64_t 
   for (int u = 0; u < U; ++u)
     if (u < K) v[u] = ld<true>(&vp[u * 64]);
   Pack<T, R> xr[U];
-  const int64_t xmax = a.nx - R;
+  const int64_t xmin = -(int64_t)(R - 1), xmax = a.nx - 1;
 #pragma unroll
   for (int u = 0; u < U; ++u)
     if (u < K) {
       const int64_t j = row0 + a.upat[u];
-      xr[u] = ld_xrun<T, R>((const T*)a.x + (j < 0 ? 0 : j > xmax ? xmax : j));
+      xr[u] = ld_xrun<T, R>((const T*)a.x + (j < xmin ? xmin : j > xmax ? xmax : j));
     }
   const int emask = d[2];
   uint64_t m = 0;
