@@ -267,7 +267,7 @@ int upload_long(pa_mat* A, const std::vector<int32_t>& lrows, const std::vector<
   A->n_long = (int64_t)lrows.size();
   A->h_long_rows = lrows;
   if (A->n_long == 0) return 0;
-  const int64_t ns = (A->nrows + A->H - 1) / A->H, W = A->H / 64;
+  const int64_t ns = (A->main.nrows + A->H - 1) / A->H, W = A->H / 64;
   std::vector<int32_t> sflags(ns, 0);
   std::vector<uint64_t> lmask(ns * W, 0);
   for (int32_t r : lrows) {
@@ -275,9 +275,10 @@ int upload_long(pa_mat* A, const std::vector<int32_t>& lrows, const std::vector<
     sflags[s] = 1;
     lmask[s * W + i / 64] |= 1ull << (i & 63);
   }
-  if (dev_upload(&A->d_long_row, lrows) || dev_upload(&A->d_long_ptr, lptr) || dev_upload(&A->d_sflags, sflags) ||
-      dev_upload(&A->d_lmask, lmask))
-    return -1;
+  HIPC(A->d_long_row.upload(lrows));
+  HIPC(A->d_long_ptr.upload(lptr));
+  HIPC(A->d_sflags.upload(sflags));
+  HIPC(A->d_lmask.upload(lmask));
   // chunks for the parallel (non-exact) mode: consecutive kLongChunk
   // entries; chunk c ends where chunk c+1 starts (the last at lptr.back())
   constexpr int64_t kLongChunk = 4096;
@@ -288,9 +289,10 @@ int upload_long(pa_mat* A, const std::vector<int32_t>& lrows, const std::vector<
   }
   A->n_lchunks = (int64_t)cstart.size();
   cstart.push_back(lptr.back());
-  if (dev_upload(&A->d_lchunk_start, cstart) || dev_upload(&A->d_lrow_chunk, rchunk)) return -1;
-  HIPC(hipMalloc(&A->d_lpart, std::max<int64_t>(A->n_lchunks, 1) * 16));
-  if (!lcol.empty() && dev_upload(&A->d_long_col, lcol)) return -1;
+  HIPC(A->d_lchunk_start.upload(cstart));
+  HIPC(A->d_lrow_chunk.upload(rchunk));
+  HIPC(A->d_lpart.alloc(std::max<int64_t>(A->n_lchunks, 1) * 16));
+  HIPC(A->d_long_col.upload(lcol));
   return 0;
 }
 
@@ -298,30 +300,55 @@ inline bool is_long_row(const pa_mat* A, int64_t r) {
   return A->n_long > 0 && std::binary_search(A->h_long_rows.begin(), A->h_long_rows.end(), (int32_t)r);
 }
 
-inline int64_t nvals(const pa_mat* A) { return A->slots + A->n_gnz + A->n_lnz; }
+inline int64_t nvals(const pa_mat* A) { return A->main.slots + A->n_gnz + A->n_lnz; }
+
+// The long rows of a matrix with these row lengths: their oids (ascending),
+// their CSR pointers, and each row's position among them (-1: a SELL row)
+struct LongRows {
+  std::vector<int32_t> lidx, lrows;
+  std::vector<int64_t> lptr{0};
+};
+LongRows split_long_rows(const std::vector<int32_t>& len) {
+  LongRows L;
+  const int32_t thr = long_threshold(len);
+  L.lidx.assign(len.size(), -1);
+  for (size_t r = 0; r < len.size(); ++r)
+    if (len[r] > thr) {
+      L.lidx[r] = (int32_t)L.lrows.size();
+      L.lrows.push_back((int32_t)r);
+      L.lptr.push_back(L.lptr.back() + len[r]);
+    }
+  return L;
+}
+
+// Slice lengths (entries per row) → the slices' slot offsets; S takes the
+// slice count, the slots and the longest row
+std::vector<int64_t> sell_offsets(Sell& S, const std::vector<int32_t>& slen, int H) {
+  std::vector<int64_t> soff(slen.size());
+  S.nslices = (int64_t)slen.size();
+  S.slots = 0;
+  S.maxlen = 0;
+  for (size_t s = 0; s < slen.size(); ++s) {
+    soff[s] = S.slots;
+    S.slots += (int64_t)slen[s] * H;
+    S.maxlen = std::max(S.maxlen, (int)slen[s]);
+  }
+  return soff;
+}
 
 int finish_sell_layout(pa_mat* A, const std::vector<int32_t>& slen, const std::vector<char>& sghost,
                        std::vector<int64_t>* soff_out) {
-  const int64_t ns = (int64_t)slen.size();
-  std::vector<int64_t> soff(ns);
-  int64_t acc = 0;
-  for (int64_t s = 0; s < ns; ++s) {
-    soff[s] = acc;
-    acc += (int64_t)slen[s] * A->H;
-  }
-  A->slots = acc;
-  A->nslices = ns;
+  std::vector<int64_t> soff = sell_offsets(A->main, slen, A->H);
   A->h_slen = slen;
-  A->maxlen_all = 0;
-  for (int32_t l : slen) A->maxlen_all = std::max(A->maxlen_all, (int)l);
   std::vector<int32_t> ilist, blist;
-  for (int64_t s = 0; s < ns; ++s) (sghost[s] ? blist : ilist).push_back((int32_t)s);
-  A->nslices_int = (int64_t)ilist.size();
-  if (dev_upload(&A->d_slice_off, soff)) return -1;
-  if (dev_upload(&A->d_slice_len, slen)) return -1;
+  for (size_t s = 0; s < slen.size(); ++s) (sghost[s] ? blist : ilist).push_back((int32_t)s);
+  A->sl_all.n_int = (int64_t)ilist.size();
+  A->sl_all.n_bnd = (int64_t)blist.size();
+  HIPC(A->main.off.upload(soff));
+  HIPC(A->main.len.upload(slen));
   if (!blist.empty()) {
-    if (dev_upload(&A->d_int_list, ilist)) return -1;
-    if (dev_upload(&A->d_bnd_list, blist)) return -1;
+    HIPC(A->sl_all.d_int.upload(ilist));
+    HIPC(A->sl_all.d_bnd.upload(blist));
   }
   if (soff_out) *soff_out = std::move(soff);
   return 0;
@@ -347,22 +374,14 @@ int finish_sell_layout(pa_mat* A, const std::vector<int32_t>& slen, const std::v
 // and U alone and issues them before its descriptor arrives; the
 // descriptor's word 2 (emask: which of U's entries the slice's pattern
 // holds) and mask only select the terms (rows_pattern_u).
-void free_uniform(pa_mat* A) {
-  dev_free(A->d_uval);
-  dev_free(A->d_uemap);
-  A->d_uval = nullptr;
-  A->d_uemap = nullptr;
-  A->uK = 0;
-}
-
 int build_uniform(pa_mat* A, const std::vector<int32_t>& kind, const std::vector<int32_t>& table,
                   const std::vector<int32_t>& packed, std::vector<int32_t>& desc) {
-  free_uniform(A);
+  A->uni = UniformRows{};
   if (!knobs().spmv_uniform || A->dtype != PA_F64 || A->R != 2 || A->npatterns == 0) return 0;
-  const int64_t ns = A->nslices, K0 = A->kmax, np = A->npatterns;
+  const int64_t ns = A->main.nslices, K0 = A->kmax, np = A->npatterns;
   std::vector<int32_t> plen(np, 0);
   for (int64_t s = 0; s < ns; ++s)
-    if (kind[s] == 1) plen[packed[s] >> 9] = packed[s] & 0xff;
+    if (kind[s] == kBkPattern) plen[packed[s] >> 9] = packed[s] & 0xff;
   std::vector<int32_t> U;
   for (int64_t p = 0; p < np; ++p)
     for (int32_t k = 0; k < plen[p]; ++k) U.push_back(table[p * K0 + k]);
@@ -384,30 +403,30 @@ int build_uniform(pa_mat* A, const std::vector<int32_t>& kind, const std::vector
     }
   const int DW = desc_words(A->R);
   for (int64_t s = 0; s < ns; ++s)
-    if (kind[s] == 1) desc[DW * s + 2] = emask[packed[s] >> 9];
+    if (kind[s] == kBkPattern) desc[DW * s + 2] = emask[packed[s] >> 9];
   hipStream_t st = A->ctx->s_main;
   const size_t S = dtype_size(A->dtype);
-  if (dev_upload(&A->d_uemap, emap)) return -1;
-  HIPC(hipMalloc(&A->d_uval, (size_t)ns * A->H * K * S));
-  HIPC(hipMemsetAsync(A->d_uval, 0, (size_t)ns * A->H * K * S, st));
-  A->uK = K;
-  for (int e = 0; e < 8; ++e) A->upat[e] = e < K ? U[e] : 0;
+  HIPC(A->uni.emap.upload(emap));
+  HIPC(A->uni.val.alloc((size_t)ns * A->H * K * S));
+  HIPC(hipMemsetAsync(A->uni.val, 0, (size_t)ns * A->H * K * S, st));
+  A->uni.K = K;
+  for (int e = 0; e < 8; ++e) A->uni.pat[e] = e < K ? U[e] : 0;
   launch_u_fill(A, st);
   HIPC(hipGetLastError());
   return 0;
 }
 
 int dedup_patterns(pa_mat* A, const std::vector<int32_t>& kind) {
-  const int64_t ns = A->nslices, K = A->kmax;
+  const int64_t ns = A->main.nslices, K = A->kmax;
   hipStream_t st = A->ctx->s_main;
-  std::vector<int32_t> pat(ns * K);
-  HIPC(hipMemcpyAsync(pat.data(), A->d_pat, ns * K * 4, hipMemcpyDeviceToHost, st));
+  std::vector<int32_t> pat;
+  HIPC(download(pat, A->d_pat.p, ns * K, st));
   HIPC(hipStreamSynchronize(st));
   std::vector<int32_t> table, packed(A->h_plen);
   std::unordered_map<std::string, int32_t> ids;
   int64_t reach = 0;  // largest |column - row| of the pattern slices' patterns
   for (int64_t s = 0; s < ns; ++s) {
-    if (kind[s] != 1) continue;
+    if (kind[s] != kBkPattern) continue;
     const int32_t len = A->h_plen[s];
     CHECK_ARG(len >= 1 && len <= 255, "pattern slice with more than 255 entries per row");
     std::string key(reinterpret_cast<const char*>(&pat[s * K]), (size_t)len * 4);
@@ -436,22 +455,20 @@ int dedup_patterns(pa_mat* A, const std::vector<int32_t>& kind) {
   // neighbour plane (FE27: the z-neighbour, N² rows away) one run-group
   // later on the same XCD, whose L2 still holds those x lines
   A->xcd_auto = (int)std::min<int64_t>(64, reach / (4 * A->H) / 8);
-  dev_free(A->d_pat);
-  A->d_pat = nullptr;
   if (table.empty()) table.assign(K, 0);
-  if (dev_upload(&A->d_pat, table)) return -1;
+  HIPC(A->d_pat.upload(table));
   HIPC(hipMemcpyAsync(A->d_plen, packed.data(), ns * 4, hipMemcpyHostToDevice, st));
   {
     // the pattern slices' descriptors (SPMV_DESC): offset / H, the length
     // word and the mask words in one aligned record per slice, so a wave
     // reads its slice's metadata with one scalar load (FD7 128^3: 0.0287 ->
     // 0.0277 ms, profiles/r06/p/)
-    std::vector<int64_t> soff(ns);
-    HIPC(hipMemcpyAsync(soff.data(), A->d_slice_off, ns * 8, hipMemcpyDeviceToHost, st));
+    std::vector<int64_t> soff;
+    HIPC(download(soff, A->main.off.p, ns, st));
     HIPC(hipStreamSynchronize(st));
     const int W = A->H / 64, DW = desc_words(A->R);
-    std::vector<uint64_t> mask(ns * W);
-    HIPC(hipMemcpyAsync(mask.data(), A->d_mask, ns * W * 8, hipMemcpyDeviceToHost, st));
+    std::vector<uint64_t> mask;
+    HIPC(download(mask, A->d_mask.p, ns * W, st));
     HIPC(hipStreamSynchronize(st));
     std::vector<int32_t> desc(DW * ns, 0);
     for (int64_t s = 0; s < ns; ++s) {
@@ -461,16 +478,12 @@ int dedup_patterns(pa_mat* A, const std::vector<int32_t>& kind) {
       std::memcpy(&desc[DW * s + 4], &mask[s * W], W * 8);
     }
     if (build_uniform(A, kind, table, packed, desc)) return -1;
-    dev_free(A->d_pdesc);
-    A->d_pdesc = nullptr;
-    if (dev_upload(&A->d_pdesc, desc)) return -1;
+    HIPC(A->d_pdesc.upload(desc));
   }
   HIPC(hipStreamSynchronize(st));
   return 0;
 }
 
-// Pattern slices + side SELL from the int32 layout (device detection, host
-// bookkeeping).  noids: owned columns (x lids >= noids are ghosts).
 // The CSC nz → slot map (pa_mat_from_csc / _coo) after k_delta16 moved the
 // delta16 slices' values to the interleaved layout: a slot of such a slice
 // at (k, lane, r) held row w = lane*R + r, which now sits at (k, w % 64,
@@ -480,70 +493,51 @@ int remap_nz_interleaved(pa_mat* A, const std::vector<int32_t>& kind, hipStream_
   if (A->d_nz_slot) {
     A->h_nz_slot.resize(A->csc_nnz);
     HIPC(hipMemcpy(A->h_nz_slot.data(), A->d_nz_slot, A->csc_nnz * 8, hipMemcpyDeviceToHost));
-    dev_free(A->d_nz_slot);
-    A->d_nz_slot = nullptr;
+    A->d_nz_slot.reset();
   }
-  const int64_t ns = A->nslices, R = A->R, H = A->H;
+  const int64_t ns = A->main.nslices, R = A->R, H = A->H;
   std::vector<int64_t> soff(ns);
-  HIPC(hipMemcpy(soff.data(), A->d_slice_off, ns * 8, hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(soff.data(), A->main.off, ns * 8, hipMemcpyDeviceToHost));
   for (int64_t& slot : A->h_nz_slot) {
     if (slot < 0) continue;
     const int64_t s = (int64_t)(std::upper_bound(soff.begin(), soff.end(), slot) - soff.begin()) - 1;
-    if (kind[s] != 3) continue;
+    if (kind[s] != kBkDelta16) continue;
     const int64_t t = slot - soff[s], k = t / H, w = t % H;  // w = lane*R + r before the move
     slot = soff[s] + (k * 64 + w % 64) * R + w / 64;
   }
   return 0;
 }
 
-void free_triple_sell(pa_mat* A) {
-  for (void* p : {(void*)A->d_t_off, (void*)A->d_t_len, (void*)A->d_t_col16, A->d_t_val, (void*)A->d_t_gbase,
-                  (void*)A->d_t_rowmap, (void*)A->d_t_src, (void*)A->d_t_rowlen, (void*)A->d_t_int_list,
-                  (void*)A->d_t_bnd_list, (void*)A->d_t_desc})
-    dev_free(p);
-  A->d_t_off = nullptr;
-  A->d_t_desc = nullptr;
-  A->d_t_len = A->d_t_gbase = A->d_t_rowmap = A->d_t_rowlen = A->d_t_int_list = A->d_t_bnd_list = nullptr;
-  A->d_t_col16 = nullptr;
-  A->d_t_val = nullptr;
-  A->d_t_src = nullptr;
-  A->t_pack = 0;
-  A->t_nrows = A->t_nslices = A->t_slots = A->t_tri_slices = A->t_tri_rows = A->t_code_slots = 0;
-  A->t_pair_slices = A->t_pair_rows = 0;
-  A->nt_int = A->nt_bnd = 0;
-  A->h_t_len.clear();
-}
-
-// The triple SELL: the rows of the delta16 slices (kind 3),
+// The triple SELL: the rows of the delta16 slices (kBkDelta16),
 // re-sliced — the rows whose columns are not all consecutive triples, then
 // the triple rows (spmv_tri_order), each class by length (descending) and
 // oid — so that most slices
 // hold only triple rows and keep one 16-bit code per triple (their lanes
 // read a triple's x as one run), and no row's values stream twice (unlike
-// the side SELL of pattern slices).  The main delta16 slices become kind 5
+// the side SELL of pattern slices).  The main delta16 slices become kBkMoved
 // (not launched in pattern mode; spmv_format 0 still runs them as int32).
 // Returns 0 without building when a slice's ghost codes would not fit.
 int build_triple_sell(pa_mat* A, std::vector<int32_t>& kind, int64_t noids) {
   hipStream_t st = A->ctx->s_main;
-  const int64_t ns = A->nslices, H = A->H, R = A->R;
+  const int64_t ns = A->main.nslices, H = A->H, R = A->R;
   std::vector<int32_t> rows;
   for (int64_t s = 0; s < ns; ++s)
-    if (kind[s] == 3)
-      for (int64_t i = s * H; i < std::min<int64_t>(A->nrows, s * H + H); ++i) rows.push_back((int32_t)i);
+    if (kind[s] == kBkDelta16)
+      for (int64_t i = s * H; i < std::min<int64_t>(A->main.nrows, s * H + H); ++i) rows.push_back((int32_t)i);
   const int64_t n = (int64_t)rows.size();
   if (n == 0) return 0;
-  int32_t *d_rows = nullptr, *d_info = nullptr;
-  if (dev_upload(&d_rows, rows)) return -1;
-  HIPC(hipMalloc((void**)&d_info, n * 4));
-  launch_t_rowinfo(A, n, d_rows, noids, d_info, st);
-  HIPC(hipGetLastError());
-  std::vector<int32_t> info(n);
-  std::vector<int64_t> soff(ns);
-  HIPC(hipMemcpyAsync(info.data(), d_info, n * 4, hipMemcpyDeviceToHost, st));
-  HIPC(hipMemcpyAsync(soff.data(), A->d_slice_off, ns * 8, hipMemcpyDeviceToHost, st));
-  HIPC(hipStreamSynchronize(st));
-  dev_free(d_rows);
-  dev_free(d_info);
+  std::vector<int32_t> info;
+  std::vector<int64_t> soff;
+  {
+    DevBuf<int32_t> d_rows, d_info;
+    HIPC(d_rows.upload(rows));
+    HIPC(d_info.alloc(n));
+    launch_t_rowinfo(A, n, d_rows, noids, d_info, st);
+    HIPC(hipGetLastError());
+    HIPC(download(info, d_info.p, n, st));
+    HIPC(download(soff, A->main.off.p, ns, st));
+    HIPC(hipStreamSynchronize(st));
+  }
   constexpr int32_t kLen = (1 << 28) - 1, kReg = 1 << 28, kGhost = 1 << 29, kBad = 1 << 30;
   for (int32_t v : info)
     if (v & kBad) return 0;
@@ -556,16 +550,14 @@ int build_triple_sell(pa_mat* A, std::vector<int32_t>& kind, int64_t noids) {
   std::vector<int64_t> pairs;  // candidate index of each pair's row a
   std::vector<char> paired(n, 0);
   if (tpack & 4) {
-    int32_t *d_rows2 = nullptr, *d_pair = nullptr;
-    if (dev_upload(&d_rows2, rows)) return -1;
-    HIPC(hipMalloc((void**)&d_pair, n * 4));
-    launch_t_pairinfo(A, n, d_rows2, d_pair, st);
+    DevBuf<int32_t> d_rows, d_pair;
+    HIPC(d_rows.upload(rows));
+    HIPC(d_pair.alloc(n));
+    launch_t_pairinfo(A, n, d_rows, d_pair, st);
     HIPC(hipGetLastError());
-    std::vector<int32_t> pairable(n);
-    HIPC(hipMemcpyAsync(pairable.data(), d_pair, n * 4, hipMemcpyDeviceToHost, st));
+    std::vector<int32_t> pairable;
+    HIPC(download(pairable, d_pair.p, n, st));
     HIPC(hipStreamSynchronize(st));
-    dev_free(d_rows2);
-    dev_free(d_pair);
     for (int64_t i = 0; i + 1 < n; ++i)
       if (pairable[i] && !paired[i] && (info[i] & kReg) && (info[i + 1] & kReg) &&
           (info[i] & kLen) == (info[i + 1] & kLen)) {
@@ -600,7 +592,7 @@ int build_triple_sell(pa_mat* A, std::vector<int32_t>& kind, int64_t noids) {
   }
   const int64_t tns = (npos + H - 1) / H;
   std::vector<int32_t> rowmap(npos, -1), rowlen(npos, 0), tlen(tns, 0), tint, tbnd;
-  std::vector<int64_t> src(npos, 0), toff(tns), nreal(tns, 0);
+  std::vector<int64_t> src(npos, 0), nreal(tns, 0);
   std::vector<char> tri(tns, 1), ghost(tns, 0);
   for (int64_t i = 0; i < npos; ++i) {
     if (at[i] < 0) continue;
@@ -619,65 +611,64 @@ int build_triple_sell(pa_mat* A, std::vector<int32_t>& kind, int64_t noids) {
   int64_t nreg = 0;
   for (int32_t v : info) nreg += (v & kReg) ? 1 : 0;
   if (4 * nreg < n) return 0;  // mostly rows without triples (e.g. FD7): the delta16 slices stay
-  int64_t acc = 0, codes = 0;
-  A->maxlen_t = 0;
+  TripleSell& T = A->tri;
+  const std::vector<int64_t> toff = sell_offsets(T, tlen, (int)H);  // (before the lengths take their flag bits)
   for (int64_t ts = 0; ts < tns; ++ts) {
-    toff[ts] = acc;
-    acc += (int64_t)tlen[ts] * H;
-    A->maxlen_t = std::max(A->maxlen_t, (int)tlen[ts]);
     if (ts * H >= pstart && npairs) {  // pair slices (regular rows: length % 3 == 0)
-      ++A->t_tri_slices;
-      ++A->t_pair_slices;
-      A->t_tri_rows += nreal[ts];
-      A->t_pair_rows += nreal[ts];
-      codes += (int64_t)tlen[ts] / 3 * 64;
+      ++T.tri_slices;
+      ++T.pair_slices;
+      T.tri_rows += nreal[ts];
+      T.pair_rows += nreal[ts];
+      T.code_slots += (int64_t)tlen[ts] / 3 * 64;
       tlen[ts] |= kTriSlice | kTriPair;
     } else if (tri[ts] && tlen[ts] % 3 == 0) {
-      ++A->t_tri_slices;
-      A->t_tri_rows += nreal[ts];
-      codes += (int64_t)tlen[ts] / 3 * H;
+      ++T.tri_slices;
+      T.tri_rows += nreal[ts];
+      T.code_slots += (int64_t)tlen[ts] / 3 * H;
       tlen[ts] |= kTriSlice;
     } else {
-      codes += (int64_t)tlen[ts] * H;
+      T.code_slots += (int64_t)tlen[ts] * H;
     }
     (ghost[ts] ? tbnd : tint).push_back((int32_t)ts);
   }
-  A->t_nrows = npos;
-  A->t_nslices = tns;
-  A->t_pack = tpack;
-  A->t_slots = acc;
-  A->t_code_slots = codes;
-  A->h_t_len = tlen;
+  T.nrows = npos;
+  T.pack = tpack;
+  T.h_len = tlen;
   const size_t S = dtype_size(A->dtype);
-  if (dev_upload(&A->d_t_off, toff) || dev_upload(&A->d_t_len, tlen) || dev_upload(&A->d_t_rowmap, rowmap) ||
-      dev_upload(&A->d_t_rowlen, rowlen) || dev_upload(&A->d_t_src, src) || dev_upload(&A->d_t_int_list, tint) ||
-      dev_upload(&A->d_t_bnd_list, tbnd))
-    return -1;
-  A->nt_int = (int64_t)tint.size();
-  A->nt_bnd = (int64_t)tbnd.size();
-  HIPC(hipMalloc((void**)&A->d_t_col16, std::max<int64_t>(acc, 1) * 2));
-  HIPC(hipMalloc(&A->d_t_val, std::max<int64_t>(acc, 1) * S));
+  const int64_t acc = T.slots;
+  HIPC(T.off.upload(toff));
+  HIPC(T.len.upload(tlen));
+  HIPC(T.rowmap.upload(rowmap));
+  HIPC(T.rowlen.upload(rowlen));
+  HIPC(T.src.upload(src));
+  HIPC(T.list.d_int.upload(tint));
+  HIPC(T.list.d_bnd.upload(tbnd));
+  T.list.n_int = (int64_t)tint.size();
+  T.list.n_bnd = (int64_t)tbnd.size();
+  HIPC(T.col16.alloc(std::max<int64_t>(acc, 1)));
+  HIPC(T.val.alloc(std::max<int64_t>(acc, 1) * S));
   // the positions past the last row of the last slice (and code groups no
   // row writes) are padding: codes 0xFFFF (column -1, never gathered), values 0
-  HIPC(hipMemsetAsync(A->d_t_col16, 0xFF, std::max<int64_t>(acc, 1) * 2, st));
-  HIPC(hipMemsetAsync(A->d_t_val, 0, std::max<int64_t>(acc, 1) * S, st));
-  HIPC(hipMalloc((void**)&A->d_t_gbase, tns * 4));
-  int32_t* d_ok = nullptr;
-  HIPC(hipMalloc((void**)&d_ok, tns * 4));
-  launch_t_gbase(A, noids, d_ok, st);
-  HIPC(hipGetLastError());
-  std::vector<int32_t> ok(tns);
-  HIPC(hipMemcpyAsync(ok.data(), d_ok, tns * 4, hipMemcpyDeviceToHost, st));
-  HIPC(hipStreamSynchronize(st));
-  dev_free(d_ok);
+  HIPC(hipMemsetAsync(A->tri.col16, 0xFF, std::max<int64_t>(acc, 1) * 2, st));
+  HIPC(hipMemsetAsync(A->tri.val, 0, std::max<int64_t>(acc, 1) * S, st));
+  HIPC(T.gbase.alloc(tns));
+  std::vector<int32_t> ok;
+  {
+    DevBuf<int32_t> d_ok;
+    HIPC(d_ok.alloc(tns));
+    launch_t_gbase(A, noids, d_ok, st);
+    HIPC(hipGetLastError());
+    HIPC(download(ok, d_ok.p, tns, st));
+    HIPC(hipStreamSynchronize(st));
+  }
   for (int32_t v : ok)
     if (!v) {  // a slice's ghost columns span more than 15 bits: keep the delta16 slices
-      free_triple_sell(A);
+      T = TripleSell{};
       return 0;
     }
   {  // one 16 B descriptor per slice (SPMV_DESC): offset / H, length word, ghost base
-    std::vector<int32_t> gbase(tns), desc(4 * tns, 0);
-    HIPC(hipMemcpyAsync(gbase.data(), A->d_t_gbase, tns * 4, hipMemcpyDeviceToHost, st));
+    std::vector<int32_t> gbase, desc(4 * tns, 0);
+    HIPC(download(gbase, T.gbase.p, tns, st));
     HIPC(hipStreamSynchronize(st));
     for (int64_t ts = 0; ts < tns; ++ts) {
       CHECK_ARG(toff[ts] / H <= INT32_MAX, "slice offset outside the descriptor's range");
@@ -685,167 +676,201 @@ int build_triple_sell(pa_mat* A, std::vector<int32_t>& kind, int64_t noids) {
       desc[4 * ts + 1] = tlen[ts];
       desc[4 * ts + 2] = gbase[ts];
     }
-    if (dev_upload(&A->d_t_desc, desc)) return -1;
+    HIPC(T.desc.upload(desc));
   }
   launch_t_fill(A, noids, true, st);
   HIPC(hipGetLastError());
-  unsigned* d_bad = nullptr;
-  unsigned bad = 0;
-  HIPC(hipMalloc((void**)&d_bad, 4));
+  DevBuf<unsigned> d_bad;
+  std::vector<unsigned> bad;
+  HIPC(d_bad.alloc(1));
   HIPC(hipMemsetAsync(d_bad, 0, 4, st));
   launch_t_check(A, d_bad, st);
   HIPC(hipGetLastError());
-  HIPC(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
+  HIPC(download(bad, d_bad.p, 1, st));
   HIPC(hipStreamSynchronize(st));
-  dev_free(d_bad);
-  CHECK_ARG(bad == 0, "triple SELL build: a column code decodes outside x (internal error)");
+  CHECK_ARG(bad[0] == 0, "triple SELL build: a column code decodes outside x (internal error)");
   for (int64_t s = 0; s < ns; ++s)
-    if (kind[s] == 3) kind[s] = 5;
+    if (kind[s] == kBkDelta16) kind[s] = kBkMoved;
   return 0;
 }
 
-int finalize_pattern(pa_mat* A, int kmax, int64_t noids, bool retry_r2) {
-  A->kmax = std::max(kmax, 1);
-  const int64_t ns = A->nslices;
-  if (ns == 0) return 0;
+// finalize_pattern's steps, in the order of their device work.
+
+// What k_pattern_detect found per slice: its kind (kBkPattern / kBkInt32),
+// whether its pattern rows read ghosts, and its regular-row bits.  The
+// device keeps d_kind, d_plen (h_plen its copy), d_pat (one row per slice,
+// until dedup_patterns) and d_mask.
+struct Detected {
+  std::vector<int32_t> kind, pghost;
+  std::vector<uint64_t> mask;
+};
+int detect_patterns(pa_mat* A, int64_t noids, Detected* D) {
+  const int64_t ns = A->main.nslices;
   hipStream_t st = A->ctx->s_main;
   const int W = A->H / 64;
-  int32_t *d_pghost = nullptr, *d_nirreg = nullptr;
-  HIPC(hipMalloc((void**)&A->d_kind, ns * 4));
-  HIPC(hipMalloc((void**)&A->d_plen, ns * 4));
-  HIPC(hipMalloc((void**)&A->d_pat, ns * A->kmax * 4));
-  HIPC(hipMalloc((void**)&A->d_mask, ns * W * 8));
-  HIPC(hipMalloc((void**)&d_pghost, ns * 4));
-  HIPC(hipMalloc((void**)&d_nirreg, ns * 4));
+  DevBuf<int32_t> d_pghost, d_nirreg;
+  HIPC(A->d_kind.alloc(ns));
+  HIPC(A->d_plen.alloc(ns));
+  HIPC(A->d_pat.alloc(ns * A->kmax));
+  HIPC(A->d_mask.alloc(ns * W));
+  HIPC(d_pghost.alloc(ns));
+  HIPC(d_nirreg.alloc(ns));
   HIPC(hipMemsetAsync(A->d_mask, 0, ns * W * 8, st));
   const int min_pct = knobs().pattern_min_pct ? knobs().pattern_min_pct : (A->R == 4 ? 50 : 70);
   launch_pattern_detect(A, noids, min_pct, A->d_kind, A->d_plen, A->d_pat, A->d_mask, d_pghost, d_nirreg, st);
   HIPC(hipGetLastError());
-  std::vector<int32_t> kind(ns), pghost(ns), nirreg(ns);
-  std::vector<uint64_t> mask(ns * W);
-  A->h_plen.resize(ns);
-  HIPC(hipMemcpyAsync(A->h_plen.data(), A->d_plen, ns * 4, hipMemcpyDeviceToHost, st));
-  HIPC(hipMemcpyAsync(kind.data(), A->d_kind, ns * 4, hipMemcpyDeviceToHost, st));
-  HIPC(hipMemcpyAsync(pghost.data(), d_pghost, ns * 4, hipMemcpyDeviceToHost, st));
-  HIPC(hipMemcpyAsync(nirreg.data(), d_nirreg, ns * 4, hipMemcpyDeviceToHost, st));
-  HIPC(hipMemcpyAsync(mask.data(), A->d_mask, ns * W * 8, hipMemcpyDeviceToHost, st));
+  std::vector<int32_t> nirreg;  // (per slice: its irregular rows; the side rows are counted from the mask)
+  HIPC(download(A->h_plen, A->d_plen.p, ns, st));
+  HIPC(download(D->kind, A->d_kind.p, ns, st));
+  HIPC(download(D->pghost, d_pghost.p, ns, st));
+  HIPC(download(nirreg, d_nirreg.p, ns, st));
+  HIPC(download(D->mask, A->d_mask.p, ns * W, st));
   HIPC(hipStreamSynchronize(st));
-  dev_free(d_pghost);
-  dev_free(d_nirreg);
-  if (retry_r2 && A->dtype == PA_F32 && A->R == 4 && knobs().f32_rows == 0) {
-    // f32_rows auto: a Float32 matrix with int32/delta16 slices (irregular
-    // parts, C5) streams faster as 128-row slices of 8 B packs, whose delta16
-    // rows take the triple SELL (C5 F32 0.0736 -> 0.0683 ms, 345 -> 289 MB);
-    // a matrix of pattern slices keeps 256-row slices (FE27 256^3 F32 0.328
-    // -> 0.374 ms with 128: profiles/r05/af/).  C5's parts hold 6-62 %
-    // pattern slices, a stencil's parts ~100 %: the cut is 80 %
-    int64_t np = 0;
-    for (int64_t s = 0; s < ns; ++s) np += kind[s] == 1;
-    if (5 * np < 4 * ns) return kPreferR2;
-  }
-  if (dedup_patterns(A, kind)) return -1;
-  if (knobs().spmv_delta16) {  // int32-column slices whose columns fit 16-bit codes (kind 3)
-    int32_t* d_ok = nullptr;
-    HIPC(hipMalloc((void**)&A->d_col16, std::max<int64_t>(A->slots, 1) * 2));
-    HIPC(hipMalloc((void**)&A->d_gbase, ns * 4));
-    HIPC(hipMalloc((void**)&d_ok, ns * 4));
+  return 0;
+}
+
+// f32_rows auto: a Float32 matrix with int32/delta16 slices (irregular
+// parts, C5) streams faster as 128-row slices of 8 B packs, whose delta16
+// rows take the triple SELL (C5 F32 0.0736 -> 0.0683 ms, 345 -> 289 MB);
+// a matrix of pattern slices keeps 256-row slices (FE27 256^3 F32 0.328
+// -> 0.374 ms with 128: profiles/r05/af/).  C5's parts hold 6-62 %
+// pattern slices, a stencil's parts ~100 %: the cut is 80 %
+bool prefers_r2(const pa_mat* A, const std::vector<int32_t>& kind) {
+  if (A->dtype != PA_F32 || A->R != 4 || knobs().f32_rows != 0) return false;
+  const int64_t ns = (int64_t)kind.size();
+  const int64_t np = std::count(kind.begin(), kind.end(), (int32_t)kBkPattern);
+  return 5 * np < 4 * ns;
+}
+
+// int32-column slices whose columns fit 16-bit codes become kBkDelta16, and
+// (spmv_tri16) their rows move to the triple SELL (kBkMoved)
+int encode_delta16(pa_mat* A, int64_t noids, std::vector<int32_t>& kind) {
+  if (!knobs().spmv_delta16) return 0;
+  const int64_t ns = A->main.nslices;
+  hipStream_t st = A->ctx->s_main;
+  std::vector<int32_t> ok;
+  {
+    DevBuf<int32_t> d_ok;
+    HIPC(A->main.col16.alloc(std::max<int64_t>(A->main.slots, 1)));
+    HIPC(A->main.gbase.alloc(ns));
+    HIPC(d_ok.alloc(ns));
     launch_delta16(A, noids, A->d_kind, d_ok, st);
     HIPC(hipGetLastError());
-    std::vector<int32_t> ok(ns);
-    HIPC(hipMemcpyAsync(ok.data(), d_ok, ns * 4, hipMemcpyDeviceToHost, st));
+    HIPC(download(ok, d_ok.p, ns, st));
     HIPC(hipStreamSynchronize(st));
-    dev_free(d_ok);
-    int64_t nd = 0;
-    for (int64_t s = 0; s < ns; ++s)
-      if (ok[s]) { kind[s] = 3; ++nd; }
-    if (nd == 0) {
-      dev_free(A->d_col16);
-      dev_free(A->d_gbase);
-      A->d_col16 = nullptr;
-      A->d_gbase = nullptr;
-    } else {
-      // Float32 delta16 slices' rows are interleaved now (k_delta16): the
-      // int32 kernel of spmv_format 0 reads the layout per slice from d_kind
-      // (3), and the CSC nz → slot map follows the moved values
-      HIPC(hipMemcpyAsync(A->d_kind, kind.data(), ns * 4, hipMemcpyHostToDevice, st));
-      if (A->nz_map && A->R == 4 && remap_nz_interleaved(A, kind, st)) return -1;
-      // the device keeps kind 3 (the int32 kernel of spmv_format 0 reads
-      // the interleaved layout from it); the host marks moved slices 5
-      // spmv_tri16 1: slices of R <= 2 rows per lane (Float64, complex,
-      // Float32 with 2 rows per lane); Float32's 4-row interleaved delta16
-      // slices already gather compactly (the triple SELL with R = 4: C5 F32
-      // +3 %, F64 -10 %, profiles/r05/d/; removed r06)
-      if (knobs().spmv_tri16 && A->R <= 2 && build_triple_sell(A, kind, noids)) return -1;
-    }
   }
-  std::vector<int32_t> pint, pbnd, xint, xbnd, dint, dbnd, side;
+  int64_t nd = 0;
+  for (int64_t s = 0; s < ns; ++s)
+    if (ok[s]) { kind[s] = kBkDelta16; ++nd; }
+  if (nd == 0) {
+    A->main.col16.reset();
+    A->main.gbase.reset();
+    return 0;
+  }
+  // Float32 delta16 slices' rows are interleaved now (k_delta16): the
+  // int32 kernel of spmv_format 0 reads the layout per slice from d_kind
+  // (kBkDelta16), and the CSC nz → slot map follows the moved values
+  HIPC(hipMemcpyAsync(A->d_kind, kind.data(), ns * 4, hipMemcpyHostToDevice, st));
+  if (A->nz_map && A->R == 4 && remap_nz_interleaved(A, kind, st)) return -1;
+  // spmv_tri16 1: slices of R <= 2 rows per lane (Float64, complex,
+  // Float32 with 2 rows per lane); Float32's 4-row interleaved delta16
+  // slices already gather compactly (the triple SELL with R = 4: C5 F32
+  // +3 %, F64 -10 %, profiles/r05/d/; removed r06)
+  if (knobs().spmv_tri16 && A->R <= 2 && build_triple_sell(A, kind, noids)) return -1;
+  return 0;
+}
+
+int upload_set(SliceSet& S, const std::vector<int32_t>& in, const std::vector<int32_t>& bnd) {
+  S.n_int = (int64_t)in.size();
+  S.n_bnd = (int64_t)bnd.size();
+  HIPC(S.d_int.upload(in));
+  HIPC(S.d_bnd.upload(bnd));
+  return 0;
+}
+
+// The launch lists of the main structure's slices by kind and phase, each
+// kind's longest row, and (returned in side) the irregular rows of the
+// pattern slices, long rows excepted
+int build_slice_lists(pa_mat* A, const std::vector<int32_t>& kind, const Detected& D, std::vector<int32_t>* side) {
+  const int64_t ns = A->main.nslices;
+  const int W = A->H / 64;
+  std::vector<int32_t> pint, pbnd, xint, xbnd, dint, dbnd;
+  A->maxlen_pat = A->maxlen_pm_int = A->maxlen_d16 = 0;
   for (int64_t s = 0; s < ns; ++s) {
-    if (kind[s] == 1) (pghost[s] ? pbnd : pint).push_back((int32_t)s);
-    else if (kind[s] == 3) (pghost[s] ? dbnd : dint).push_back((int32_t)s);
-    else if (kind[s] == 0) (pghost[s] ? xbnd : xint).push_back((int32_t)s);  // (5: in the triple SELL)
-    if (kind[s] == 1) {
-      ++A->npattern_slices;
-      const int64_t nvalid = std::min<int64_t>(A->H, A->nrows - s * A->H);
-      for (int64_t i = 0; i < nvalid; ++i) {
-        if ((mask[s * W + i / 64] >> (i & 63)) & 1ull) ++A->nregular_rows;
-        else if (!is_long_row(A, s * A->H + i)) side.push_back((int32_t)(s * A->H + i));
-      }
+    const bool g = D.pghost[s] != 0;
+    switch (kind[s]) {
+      case kBkPattern:
+        (g ? pbnd : pint).push_back((int32_t)s);
+        A->maxlen_pat = std::max(A->maxlen_pat, (int)A->h_plen[s]);
+        break;
+      case kBkDelta16:
+        (g ? dbnd : dint).push_back((int32_t)s);
+        A->maxlen_d16 = std::max(A->maxlen_d16, (int)A->h_slen[s]);
+        break;
+      case kBkInt32:
+        (g ? xbnd : xint).push_back((int32_t)s);
+        A->maxlen_pm_int = std::max(A->maxlen_pm_int, (int)A->h_slen[s]);
+        break;
+      default: break;  // kBkMoved: in the triple SELL
+    }
+    if (kind[s] != kBkPattern) continue;
+    ++A->npattern_slices;
+    const int64_t nvalid = std::min<int64_t>(A->H, A->main.nrows - s * A->H);
+    for (int64_t i = 0; i < nvalid; ++i) {
+      if ((D.mask[s * W + i / 64] >> (i & 63)) & 1ull) ++A->nregular_rows;
+      else if (!is_long_row(A, s * A->H + i)) side->push_back((int32_t)(s * A->H + i));
     }
   }
   A->h_kind = kind;
-  A->maxlen_pat = A->maxlen_pm_int = A->maxlen_d16 = 0;
-  for (int64_t s = 0; s < ns; ++s) {
-    if (kind[s] == 1) A->maxlen_pat = std::max(A->maxlen_pat, (int)A->h_plen[s]);
-    else if (kind[s] == 0) A->maxlen_pm_int = std::max(A->maxlen_pm_int, (int)A->h_slen[s]);
-    else if (kind[s] == 3) A->maxlen_d16 = std::max(A->maxlen_d16, (int)A->h_slen[s]);
-  }
-  A->np_int = (int64_t)pint.size();
-  A->np_bnd = (int64_t)pbnd.size();
-  A->nx_int = (int64_t)xint.size();
-  A->nx_bnd = (int64_t)xbnd.size();
-  A->nd_int = (int64_t)dint.size();
-  A->nd_bnd = (int64_t)dbnd.size();
-  if (dev_upload(&A->d_pint_list, pint) || dev_upload(&A->d_pbnd_list, pbnd) ||
-      dev_upload(&A->d_xint_list, xint) || dev_upload(&A->d_xbnd_list, xbnd) ||
-      dev_upload(&A->d_dint_list, dint) || dev_upload(&A->d_dbnd_list, dbnd))
-    return -1;
-  // side SELL
-  A->s_nrows = (int64_t)side.size();
+  return upload_set(A->sl_pat, pint, pbnd) || upload_set(A->sl_i32, xint, xbnd) || upload_set(A->sl_d16, dint, dbnd);
+}
+
+// side SELL: the rows `rows` (oids = structure rows through side.rowmap)
+int build_side_sell(pa_mat* A, const std::vector<int32_t>& rows, int64_t noids) {
+  Sell& S = A->side;
+  S.nrows = (int64_t)rows.size();
+  if (S.nrows == 0) return 0;
+  hipStream_t st = A->ctx->s_main;
+  const int64_t H = A->H, nss = (S.nrows + H - 1) / H;
   std::vector<int32_t> rl;  // entries per side row
-  if (A->s_nrows > 0) {
-    // the side rows (oids = structure rows) through d_s_rowmap
-    if (dev_upload(&A->d_s_rowmap, side)) return -1;
-    int32_t* srow = A->d_s_rowmap;
-    int32_t* d_dummy = nullptr;
-    A->s_nslices = (A->s_nrows + A->H - 1) / A->H;
-    HIPC(hipMalloc((void**)&A->d_s_rowlen, A->s_nrows * 4));
-    HIPC(hipMalloc((void**)&d_dummy, A->s_nslices * 4));
-    HIPC(hipMemsetAsync(d_dummy, 0, A->s_nslices * 4, st));
-    launch_side_len(A, A->s_nrows, srow, A->d_s_rowlen, noids, d_dummy, st);
+  {
+    HIPC(S.rowmap.upload(rows));
+    DevBuf<int32_t> d_sghost;  // k_side_len's per-slice ghost flags (not used: side rows run after the halo)
+    HIPC(S.rowlen.alloc(S.nrows));
+    HIPC(d_sghost.alloc(nss));
+    HIPC(hipMemsetAsync(d_sghost, 0, nss * 4, st));
+    launch_side_len(A, S.nrows, S.rowmap, S.rowlen, noids, d_sghost, st);
     HIPC(hipGetLastError());
-    rl.resize(A->s_nrows);
-    HIPC(hipMemcpyAsync(rl.data(), A->d_s_rowlen, A->s_nrows * 4, hipMemcpyDeviceToHost, st));
-    HIPC(hipStreamSynchronize(st));
-    dev_free(d_dummy);
-  }
-  if (A->s_nrows > 0) {
-    int32_t* srow = A->d_s_rowmap;
-    std::vector<int32_t> slen(A->s_nslices, 0);
-    std::vector<int64_t> soff(A->s_nslices);
-    for (int64_t i = 0; i < A->s_nrows; ++i) slen[i / A->H] = std::max(slen[i / A->H], rl[i]);
-    A->maxlen_side = 0;
-    for (int32_t l : slen) A->maxlen_side = std::max(A->maxlen_side, (int)l);
-    int64_t acc = 0;
-    for (int64_t s = 0; s < A->s_nslices; ++s) { soff[s] = acc; acc += (int64_t)slen[s] * A->H; }
-    A->s_slots = acc;
-    if (dev_upload(&A->d_s_off, soff) || dev_upload(&A->d_s_len, slen)) return -1;
-    const size_t S = dtype_size(A->dtype);
-    HIPC(hipMalloc((void**)&A->d_s_col, std::max<int64_t>(acc, 1) * 4));
-    HIPC(hipMalloc(&A->d_s_val, std::max<int64_t>(acc, 1) * S));
-    launch_side_fill(A, srow, A->d_s_rowlen, st);
-    HIPC(hipGetLastError());
+    HIPC(download(rl, S.rowlen.p, S.nrows, st));
     HIPC(hipStreamSynchronize(st));
   }
+  std::vector<int32_t> slen(nss, 0);
+  for (int64_t i = 0; i < S.nrows; ++i) slen[i / H] = std::max(slen[i / H], rl[i]);
+  const std::vector<int64_t> soff = sell_offsets(S, slen, (int)H);
+  HIPC(S.off.upload(soff));
+  HIPC(S.len.upload(slen));
+  HIPC(S.col.alloc(std::max<int64_t>(S.slots, 1)));
+  HIPC(S.val.alloc(std::max<int64_t>(S.slots, 1) * dtype_size(A->dtype)));
+  launch_side_fill(A, S.rowmap, S.rowlen, st);
+  HIPC(hipGetLastError());
+  HIPC(hipStreamSynchronize(st));
+  return 0;
+}
+
+// Pattern slices + side SELL from the int32 layout (device detection, host
+// bookkeeping).  noids: owned columns (x lids >= noids are ghosts).
+// Returns kPreferR2 (nothing built past the detection) when retry_r2 and
+// the matrix is better off with 2 rows per lane (prefers_r2).
+int finalize_pattern(pa_mat* A, int kmax, int64_t noids, bool retry_r2) {
+  A->kmax = std::max(kmax, 1);
+  if (A->main.nslices == 0) return 0;
+  Detected D;
+  if (detect_patterns(A, noids, &D)) return -1;
+  if (retry_r2 && prefers_r2(A, D.kind)) return kPreferR2;
+  std::vector<int32_t> kind = D.kind, side;
+  if (dedup_patterns(A, kind) || encode_delta16(A, noids, kind) || build_slice_lists(A, kind, D, &side) ||
+      build_side_sell(A, side, noids))
+    return -1;
   A->has_pat = true;
   return 0;
 }
@@ -950,9 +975,6 @@ int build_pull(int i, int n, pa_xchg* const xg[], const LocalSet& L, int dtype, 
     for (int64_t t = 0; t < cnt; ++t) { bid[orcv[k] + t] = b; elem[orcv[k] + t] = qo[m] + t; }
   }
   if (dev_upload(&P.d_bid, bid) || dev_upload(&P.d_elem, elem) || dev_upload(&P.d_bases, bases)) return -1;
-  P.h_bid = std::move(bid);
-  P.h_elem = std::move(elem);
-  P.h_bases = std::move(bases);
   P.ok = true;
   return 0;
 }
@@ -995,8 +1017,6 @@ int build_direct(int i, int n, pa_xchg* const xg[], const LocalSet& L) {
   }
   HIPC(hipSetDevice(X->ctx->device));
   if (dev_upload(&P.d_bid, bid) || dev_upload(&P.d_elem, elem)) return -1;
-  P.h_bid = std::move(bid);
-  P.h_elem = std::move(elem);
   P.ok = true;
   return 0;
 }
@@ -2281,38 +2301,58 @@ int pa_vec_axpby(pa_vec* y, const pa_vec* x, const pa_index* idx, const void* a,
 // after the slots for exchange!/assemble!(A); nz positions index nzval.
 extern "C++" {
 namespace {
+// The frame of the three builders (mat_from_visit, mat_from_coo_impl,
+// pa_mat_stencil).  A matrix under construction lives in a unique_ptr until
+// mat_finish hands it out, so every early return frees what was allocated.
+std::unique_ptr<pa_mat> mat_start(pa_ctx* c, int dtype, int64_t nrows, int64_t ncols_lids) {
+  std::unique_ptr<pa_mat> A(new pa_mat());
+  A->ctx = c;
+  A->dtype = dtype;
+  A->R = sell_rows_per_lane(dtype);
+  A->H = 64 * A->R;
+  A->main.nrows = nrows;
+  A->ncols_lids = ncols_lids;
+  return A;
+}
+
+// The end of a build: the pattern layout over the int32 layout of slice
+// lengths slen (pattern: the columns allow one), then *out.  rebuild (may
+// be empty): builds the matrix again from the builder's arguments; a
+// Float32 matrix built with 4 rows per lane that finalize_pattern would
+// rather have with 2 (kPreferR2) is dropped and built again under f32_rows 2.
+int mat_finish(std::unique_ptr<pa_mat>& A, const std::vector<int32_t>& slen, int64_t noids, bool pattern,
+               const std::function<int()>& rebuild, pa_mat** out) {
+  if (pattern) {
+    const int kmax = slen.empty() ? 0 : *std::max_element(slen.begin(), slen.end());
+    const int rc = finalize_pattern(A.get(), kmax, noids, (bool)rebuild);
+    if (rc == kPreferR2) {
+      A.reset();
+      ForceF32Rows f(2);
+      return rebuild();
+    }
+    if (rc) return -1;
+  }
+  *out = A.release();
+  return 0;
+}
+
 template <class Visit>
 int mat_from_visit(pa_ctx* c, int dtype, int64_t nrows_lids, int64_t ncols_lids, int64_t in_nnz,
                    const void* nzval, const pa_index* rows, const pa_index* cols, Visit&& visit,
                    const char* range_error, bool csr, pa_mat** out) {
   const size_t S = dtype_size(dtype);
-  pa_mat* A = new pa_mat();
+  std::unique_ptr<pa_mat> A = mat_start(c, dtype, rows->noids, ncols_lids);
   A->csr = csr;
-  A->ctx = c;
-  A->dtype = dtype;
-  A->R = sell_rows_per_lane(dtype);
-  A->H = 64 * A->R;
-  A->nrows = rows->noids;
-  A->ncols_lids = ncols_lids;
   A->csc_nnz = in_nnz;
-  const int64_t nr = A->nrows;
+  const int64_t nr = A->main.nrows;
   std::vector<int32_t> len(nr, 0);
   std::vector<char> has_ghost(nr, 0);
-  if (visit([&](int64_t r, int64_t, int64_t, bool g) { ++len[r]; if (g) has_ghost[r] = 1; })) {
-    delete A;
-    PA_FAIL(range_error);
-  }
+  if (visit([&](int64_t r, int64_t, int64_t, bool g) { ++len[r]; if (g) has_ghost[r] = 1; })) PA_FAIL(range_error);
   const int64_t ns = (nr + A->H - 1) / A->H;
   // long rows (row-length histogram) leave the SELL
-  const int32_t thr = long_threshold(len);
-  std::vector<int32_t> lidx(nr, -1), lrows;
-  std::vector<int64_t> lptr{0};
-  for (int64_t r = 0; r < nr; ++r)
-    if (len[r] > thr) {
-      lidx[r] = (int32_t)lrows.size();
-      lrows.push_back((int32_t)r);
-      lptr.push_back(lptr.back() + len[r]);
-    }
+  const LongRows L = split_long_rows(len);
+  const std::vector<int32_t>& lidx = L.lidx;
+  const std::vector<int64_t>& lptr = L.lptr;
   A->n_lnz = lptr.back();
   std::vector<int32_t> slen(ns, 0);
   std::vector<char> sghost(ns, 0);
@@ -2325,9 +2365,9 @@ int mat_from_visit(pa_ctx* c, int dtype, int64_t nrows_lids, int64_t ncols_lids,
   }
   A->nnz = nnz;
   std::vector<int64_t> soff;
-  if (finish_sell_layout(A, slen, sghost, &soff)) { pa_mat_destroy(A); return -1; }
-  std::vector<int32_t> hcol(A->slots, -1);
-  std::vector<unsigned char> hval(A->slots * S, 0);
+  if (finish_sell_layout(A.get(), slen, sghost, &soff)) return -1;
+  std::vector<int32_t> hcol(A->main.slots, -1);
+  std::vector<unsigned char> hval(A->main.slots * S, 0);
   std::vector<int32_t> lcol(A->n_lnz);
   std::vector<unsigned char> lval(A->n_lnz * S);
   std::vector<int64_t> lpos(in_nnz, -1);  // input nz → position in the long CSR
@@ -2353,38 +2393,28 @@ int mat_from_visit(pa_ctx* c, int dtype, int64_t nrows_lids, int64_t ncols_lids,
     A->h_nz_slot[p] = slot;
   });
   // ghost-row nonzeros (dropped by the SpMV, kept for exchange!/assemble!(A)),
-  // then the long rows' values: both after the SELL slots in d_val
+  // then the long rows' values: both after the SELL slots in main.val
   for (int64_t p = 0; p < in_nnz; ++p)
     if (A->h_nz_slot[p] < 0 && lpos[p] < 0) A->h_nz_slot[p] = -(++A->n_gnz);
-  A->long_off = A->slots + A->n_gnz;
+  A->long_off = A->main.slots + A->n_gnz;
   for (int64_t p = 0; p < in_nnz; ++p)
     if (lpos[p] >= 0) A->h_nz_slot[p] = -(A->n_gnz + lpos[p] + 1);
-  hval.resize(nvals(A) * S);
+  const int64_t nv = nvals(A.get());
+  hval.resize(nv * S);
   for (int64_t p = 0; p < in_nnz; ++p)
     if (A->h_nz_slot[p] < 0 && lpos[p] < 0)
-      std::memcpy(&hval[(A->slots - A->h_nz_slot[p] - 1) * S], (const unsigned char*)nzval + p * S, S);
+      std::memcpy(&hval[(A->main.slots - A->h_nz_slot[p] - 1) * S], (const unsigned char*)nzval + p * S, S);
   if (A->n_lnz) std::memcpy(&hval[A->long_off * S], lval.data(), A->n_lnz * S);
-  if (dev_upload(&A->d_col, hcol)) { pa_mat_destroy(A); return -1; }
-  if (nvals(A)) {
-    HIPC(hipMalloc(&A->d_val, nvals(A) * S));
-    HIPC(hipMemcpy(A->d_val, hval.data(), nvals(A) * S, hipMemcpyHostToDevice));
+  HIPC(A->main.col.upload(hcol));
+  if (nv) {
+    HIPC(A->main.val.alloc(nv * S));
+    HIPC(hipMemcpy(A->main.val, hval.data(), nv * S, hipMemcpyHostToDevice));
   }
-  if (upload_long(A, lrows, lptr, lcol)) { pa_mat_destroy(A); return -1; }
+  if (upload_long(A.get(), L.lrows, lptr, lcol)) return -1;
   // pattern slices need "x lid >= noids ⇔ ghost column" (contiguous layout)
-  if (cols->own_contig && cols->ghost_contig) {
-    int kmax = 0;
-    for (int32_t l : slen) kmax = std::max(kmax, l);
-    const int rc = finalize_pattern(A, kmax, cols->noids, true);
-    if (rc == kPreferR2) {
-      pa_mat_destroy(A);
-      ForceF32Rows f(2);
-      return mat_from_visit(c, dtype, nrows_lids, ncols_lids, in_nnz, nzval, rows, cols, visit, range_error, csr,
-                            out);
-    }
-    if (rc) { pa_mat_destroy(A); return -1; }
-  }
-  *out = A;
-  return 0;
+  return mat_finish(A, slen, cols->noids, cols->own_contig && cols->ghost_contig, [&] {
+    return mat_from_visit(c, dtype, nrows_lids, ncols_lids, in_nnz, nzval, rows, cols, visit, range_error, csr, out);
+  }, out);
 }
 
 }  // namespace
@@ -2495,11 +2525,6 @@ struct SetupTrace {
     t = n;
   }
 };
-struct DevBufs {
-  std::vector<void*> p;
-  ~DevBufs() { for (void* q : p) dev_free(q); }
-  void add(void* q) { p.push_back(q); }
-};
 }  // namespace
 
 namespace {
@@ -2574,15 +2599,15 @@ int mat_from_coo_impl(pa_ctx* c, int dtype, int index_bytes, int ids_global, int
   hipStream_t st = c->s_main;
   const size_t S = dtype_size(dtype);
   SetupTrace tr(st);
-  DevBufs tmp, inp;
-  void *dI = nullptr, *dJ = nullptr, *dV = nullptr;
+  // the arrays coo_compress and coo_row_order allocate are adopted as they return
+  DevBuf<void> dI, dJ, dV, cval;
+  DevBuf<int32_t> crow, ccol, rl2o, cl2o, slen_d, sghost_d, lidx_d, lcol_d;
+  DevBuf<int64_t> dcolptr, idx2, rowptr, gflag, grank, lptr_d, nzs;
+  DevBuf<uint64_t> key2;
   if (ncoo > 0) {
-    HIPC(hipMalloc(&dI, ncoo * index_bytes));
-    inp.add(dI);
-    HIPC(hipMalloc(&dJ, ncoo * index_bytes));
-    inp.add(dJ);
-    HIPC(hipMalloc(&dV, ncoo * S));
-    inp.add(dV);
+    HIPC(dI.alloc(ncoo * index_bytes));
+    HIPC(dJ.alloc(ncoo * index_bytes));
+    HIPC(dV.alloc(ncoo * S));
     HIPC(hipMemcpy(dI, I, ncoo * index_bytes, kind));
     HIPC(hipMemcpy(dJ, J, ncoo * index_bytes, kind));
     HIPC(hipMemcpy(dV, V, ncoo * S, kind));
@@ -2596,16 +2621,18 @@ int mat_from_coo_impl(pa_ctx* c, int dtype, int index_bytes, int ids_global, int
   }
   tr.mark("upload / to_lids!");
   int64_t nu = 0;
-  int32_t *crow = nullptr, *ccol = nullptr;
-  void* cval = nullptr;
-  int64_t* dcolptr = nullptr;
   hipError_t e = hipSuccess;
-  const int rc = coo_compress(dtype, index_bytes, nrows_lids, ncols_lids, ncoo, dI, dJ, dV, csr ? 1 : 0, &nu, &crow,
-                              &ccol, &cval, &dcolptr, st, &e);
-  if (rc < 0) HIPC(e);
-  CHECK_ARG(rc == 0, "sparse: COO index out of range (BoundsError)");
-  tmp.add(crow); tmp.add(ccol); tmp.add(cval); tmp.add(dcolptr);
-  for (void*& q : inp.p) { dev_free(q); q = nullptr; }  // the COO input is no longer needed
+  {
+    int32_t *pr = nullptr, *pc = nullptr;
+    void* pv = nullptr;
+    int64_t* pp = nullptr;
+    const int rc = coo_compress(dtype, index_bytes, nrows_lids, ncols_lids, ncoo, dI, dJ, dV, csr ? 1 : 0, &nu, &pr, &pc,
+                                &pv, &pp, st, &e);
+    crow.adopt(pr), ccol.adopt(pc), cval.adopt(pv), dcolptr.adopt(pp);
+    if (rc < 0) HIPC(e);
+    CHECK_ARG(rc == 0, "sparse: COO index out of range (BoundsError)");
+  }
+  dI.reset(), dJ.reset(), dV.reset();  // the COO input is no longer needed
   tr.mark("sparse (sort, combine)");
   *csc_nnz = nu;
   const int64_t nptr = csr ? nrows_lids : ncols_lids;
@@ -2621,60 +2648,44 @@ int mat_from_coo_impl(pa_ctx* c, int dtype, int index_bytes, int ids_global, int
     for (int64_t p = 0; p < nu; ++p) rowval_out[p] = (int64_t)rv[p] + base;
   }
   tr.mark("CSC pattern to host");
-  int32_t *rl2o = nullptr, *cl2o = nullptr;
-  if (dev_upload(&rl2o, rows->h_lid_to_ohid) || dev_upload(&cl2o, cols->h_lid_to_ohid)) return -1;
-  tmp.add(rl2o); tmp.add(cl2o);
+  HIPC(rl2o.upload(rows->h_lid_to_ohid));
+  HIPC(cl2o.upload(cols->h_lid_to_ohid));
 
-  pa_mat* A = new pa_mat();
-  A->ctx = c;
-  A->dtype = dtype;
+  std::unique_ptr<pa_mat> A = mat_start(c, dtype, rows->noids, ncols_lids);
   A->csr = csr;
-  A->R = sell_rows_per_lane(dtype);
-  A->H = 64 * A->R;
-  A->nrows = rows->noids;
-  A->ncols_lids = ncols_lids;
   A->csc_nnz = nu;
-  uint64_t* key2 = nullptr;
-  int64_t *idx2 = nullptr, *rowptr = nullptr, *gflag = nullptr, *grank = nullptr, *nzs = nullptr;
-  int32_t *slen_d = nullptr, *sghost_d = nullptr;
+  const int64_t nrows = A->main.nrows;
   int64_t nnz = 0, ngh = 0;
-  if (coo_row_order(nu, crow, ccol, rl2o, cl2o, A->nrows, cols->noids, ncols_lids, A->H, &key2, &idx2, &rowptr,
-                    &gflag, &grank, &slen_d, &sghost_d, &nnz, &ngh, st, &e)) {
-    delete A;
-    HIPC(e);
+  {
+    uint64_t* pk = nullptr;
+    int64_t *pi = nullptr, *pr = nullptr, *pf = nullptr, *pg = nullptr;
+    int32_t *pl = nullptr, *ps = nullptr;
+    const int rc = coo_row_order(nu, crow, ccol, rl2o, cl2o, nrows, cols->noids, ncols_lids, A->H, &pk, &pi, &pr, &pf,
+                                 &pg, &pl, &ps, &nnz, &ngh, st, &e);
+    key2.adopt(pk), idx2.adopt(pi), rowptr.adopt(pr), gflag.adopt(pf), grank.adopt(pg), slen_d.adopt(pl),
+        sghost_d.adopt(ps);
+    if (rc) HIPC(e);
   }
-  tmp.add(key2); tmp.add(idx2); tmp.add(rowptr); tmp.add(gflag); tmp.add(grank); tmp.add(slen_d); tmp.add(sghost_d);
   tr.mark("row order");
   A->nnz = nnz;
-  const int64_t ns = (A->nrows + A->H - 1) / A->H;
+  const int64_t ns = (nrows + A->H - 1) / A->H;
   // row-length histogram → long rows (they leave the SELL, see long_threshold)
-  std::vector<int32_t> lrows;
-  std::vector<int64_t> lptr{0};
-  int32_t *lidx_d = nullptr, *lcol_d = nullptr;
-  int64_t* lptr_d = nullptr;
-  if (A->nrows > 0) {
-    std::vector<int64_t> rp(A->nrows + 1);
+  LongRows L;
+  if (nrows > 0) {
+    std::vector<int64_t> rp(nrows + 1);
     HIPC(hipStreamSynchronize(st));  // (hipMemcpy runs on the null stream)
-    HIPC(hipMemcpy(rp.data(), rowptr, (A->nrows + 1) * 8, hipMemcpyDeviceToHost));
-    std::vector<int32_t> len(A->nrows);
-    for (int64_t r = 0; r < A->nrows; ++r) len[r] = (int32_t)(rp[r + 1] - rp[r]);
-    const int32_t thr = long_threshold(len);
-    std::vector<int32_t> lidx(A->nrows, -1);
-    for (int64_t r = 0; r < A->nrows; ++r)
-      if (len[r] > thr) {
-        lidx[r] = (int32_t)lrows.size();
-        lrows.push_back((int32_t)r);
-        lptr.push_back(lptr.back() + len[r]);
-      }
-    if (!lrows.empty()) {
-      if (dev_upload(&lidx_d, lidx) || dev_upload(&lptr_d, lptr)) return -1;
-      tmp.add(lidx_d);
-      tmp.add(lptr_d);
-      HIPC(hipMalloc((void**)&lcol_d, lptr.back() * 4));
+    HIPC(hipMemcpy(rp.data(), rowptr, (nrows + 1) * 8, hipMemcpyDeviceToHost));
+    std::vector<int32_t> len(nrows);
+    for (int64_t r = 0; r < nrows; ++r) len[r] = (int32_t)(rp[r + 1] - rp[r]);
+    L = split_long_rows(len);
+    if (!L.lrows.empty()) {
+      HIPC(lidx_d.upload(L.lidx));
+      HIPC(lptr_d.upload(L.lptr));
+      HIPC(lcol_d.alloc(L.lptr.back()));
     }
   }
-  A->n_lnz = lptr.back();
-  coo_slices(ns, A->nrows, A->H, rowptr, key2, ncols_lids, cols->noids, lidx_d, slen_d, sghost_d, st);
+  A->n_lnz = L.lptr.back();
+  coo_slices(ns, nrows, A->H, rowptr, key2, ncols_lids, cols->noids, lidx_d, slen_d, sghost_d, st);
   HIPC(hipGetLastError());
   HIPC(hipStreamSynchronize(st));  // the copies below run on the null stream
   std::vector<int32_t> slen(ns), sg(ns);
@@ -2684,44 +2695,38 @@ int mat_from_coo_impl(pa_ctx* c, int dtype, int index_bytes, int ids_global, int
     HIPC(hipMemcpy(sg.data(), sghost_d, ns * 4, hipMemcpyDeviceToHost));
   }
   for (int64_t s = 0; s < ns; ++s) sghost[s] = sg[s] ? 1 : 0;
-  if (finish_sell_layout(A, slen, sghost, nullptr)) { pa_mat_destroy(A); return -1; }
-  if (A->slots > 0) {
-    HIPC(hipMalloc((void**)&A->d_col, A->slots * 4));
-    launch_fill_i32(A->slots, A->d_col, -1, st);
+  if (finish_sell_layout(A.get(), slen, sghost, nullptr)) return -1;
+  if (A->main.slots > 0) {
+    HIPC(A->main.col.alloc(A->main.slots));
+    launch_fill_i32(A->main.slots, A->main.col, -1, st);
   }
   A->n_gnz = ngh;
-  A->long_off = A->slots + ngh;
-  if (nvals(A) > 0) {
-    HIPC(hipMalloc(&A->d_val, nvals(A) * S));
-    HIPC(hipMemsetAsync(A->d_val, 0, nvals(A) * S, st));
+  A->long_off = A->main.slots + ngh;
+  const int64_t nv = nvals(A.get());
+  if (nv > 0) {
+    HIPC(A->main.val.alloc(nv * S));
+    HIPC(hipMemsetAsync(A->main.val, 0, nv * S, st));
   }
-  if (nu > 0) HIPC(hipMalloc((void**)&nzs, nu * 8));
-  A->d_nz_slot = nzs;  // downloaded on first use (load_nz_map)
-  A->nz_map = true;
+  if (nu > 0) HIPC(nzs.alloc(nu));
   tr.mark("slices");
-  coo_fill(dtype, nnz, nu, key2, idx2, rowptr, A->d_slice_off, A->H, A->R, ncols_lids, ccol, cval, gflag, grank,
-           A->slots, A->d_col, A->d_val, nzs, lidx_d, lptr_d, lcol_d, A->long_off, st);
+  coo_fill(dtype, nnz, nu, key2, idx2, rowptr, A->main.off, A->H, A->R, ncols_lids, ccol, cval, gflag, grank,
+           A->main.slots, A->main.col, A->main.val, nzs, lidx_d, lptr_d, lcol_d, A->long_off, st);
   HIPC(hipGetLastError());
+  A->d_nz_slot = std::move(nzs);  // downloaded on first use (load_nz_map)
+  A->nz_map = true;
   tr.mark("SELL fill");
-  if (upload_long(A, lrows, lptr, {})) { pa_mat_destroy(A); return -1; }
-  A->d_long_col = lcol_d;
+  if (upload_long(A.get(), L.lrows, L.lptr, {})) return -1;
+  A->d_long_col = std::move(lcol_d);
   HIPC(hipStreamSynchronize(st));
   tr.mark("long rows");
-  if (cols->own_contig && cols->ghost_contig) {
-    int kmax = 0;
-    for (int32_t l : slen) kmax = std::max(kmax, l);
-    const int rc = finalize_pattern(A, kmax, cols->noids, true);
-    if (rc == kPreferR2) {
-      pa_mat_destroy(A);
-      ForceF32Rows f(2);
-      return mat_from_coo_impl(c, dtype, index_bytes, ids_global, nrows_lids, ncols_lids, ncoo, I, J, V, kind, rows,
-                               cols, csr_bi, csc_nnz, colptr_out, rowval_out, out);
-    }
-    if (rc) { pa_mat_destroy(A); return -1; }
-  }
-  tr.mark("pattern slices");
-  *out = A;
-  return 0;
+  bool again = false;
+  const int rc = mat_finish(A, slen, cols->noids, cols->own_contig && cols->ghost_contig, [&] {
+    again = true;
+    return mat_from_coo_impl(c, dtype, index_bytes, ids_global, nrows_lids, ncols_lids, ncoo, I, J, V, kind, rows, cols,
+                             csr_bi, csc_nnz, colptr_out, rowval_out, out);
+  }, out);
+  if (rc == 0 && !again) tr.mark("pattern slices");
+  return rc;
 }
 }  // namespace
 
@@ -2994,29 +2999,28 @@ static int load_nz_map(const pa_mat* cA) {
     HIPC(hipStreamSynchronize(A->ctx->s_main));
     A->h_nz_slot.resize(A->csc_nnz);
     HIPC(hipMemcpy(A->h_nz_slot.data(), A->d_nz_slot, A->csc_nnz * 8, hipMemcpyDeviceToHost));
-    dev_free(A->d_nz_slot);
-    A->d_nz_slot = nullptr;
+    A->d_nz_slot.reset();
   }
   return 0;
 }
 
-// value index of CSC nz p in d_val (main slot, or ghost-row value after the slots)
+// value index of CSC nz p in main.val (main slot, or ghost-row value after the slots)
 static inline int64_t nz_index(const pa_mat* A, int64_t p) {
   const int64_t s = A->h_nz_slot[p];
-  return s >= 0 ? s : A->slots - s - 1;
+  return s >= 0 ? s : A->main.slots - s - 1;
 }
 
 // refresh the side SELL's copies of the irregular rows' values
 static int refresh_side(pa_mat* A, hipStream_t st) {
-  if (A->s_nrows > 0) {
-    launch_side_fill(A, A->d_s_rowmap, A->d_s_rowlen, st);
+  if (A->side.nrows > 0) {
+    launch_side_fill(A, A->side.rowmap, A->side.rowlen, st);
     HIPC(hipGetLastError());
   }
-  if (A->t_nrows > 0) {  // and the triple SELL's (values only: the columns are unchanged)
+  if (A->tri.nrows > 0) {  // and the triple SELL's (values only: the columns are unchanged)
     launch_t_fill(A, 0, false, st);
     HIPC(hipGetLastError());
   }
-  if (A->d_uval) {  // and the uniform layout's (build_uniform)
+  if (A->uni.val) {  // and the uniform layout's (build_uniform)
     launch_u_fill(A, st);
     HIPC(hipGetLastError());
   }
@@ -3033,7 +3037,7 @@ int pa_mat_set_values(pa_mat* A, const void* nzval) {
   for (int64_t p = 0; p < A->csc_nnz; ++p)
     std::memcpy(&hval[nz_index(A, p) * S], (const unsigned char*)nzval + p * S, S);
   HIPC(hipStreamSynchronize(A->ctx->s_main));
-  if (nv) HIPC(hipMemcpy(A->d_val, hval.data(), nv * S, hipMemcpyHostToDevice));
+  if (nv) HIPC(hipMemcpy(A->main.val, hval.data(), nv * S, hipMemcpyHostToDevice));
   if (refresh_side(A, A->ctx->s_main)) return -1;
   HIPC(hipStreamSynchronize(A->ctx->s_main));
   return 0;
@@ -3046,7 +3050,7 @@ int pa_mat_fillstored(pa_mat* A, const void* v) {
   CHECK_ARG(A && v, "null argument");
   HIPC(hipSetDevice(A->ctx->device));
   const int64_t nv = nvals(A);
-  if (nv) launch_fill(A->dtype, nv, 0, nullptr, A->d_val, v, A->ctx->s_main);
+  if (nv) launch_fill(A->dtype, nv, 0, nullptr, A->main.val, v, A->ctx->s_main);
   HIPC(hipGetLastError());
   if (refresh_side(A, A->ctx->s_main)) return -1;
   return 0;
@@ -3061,14 +3065,14 @@ int pa_mat_get_values(const pa_mat* A, void* nzval) {
   std::vector<unsigned char> hval(nv * S, 0);
   HIPC(hipStreamSynchronize(A->ctx->s_comm));
   HIPC(hipStreamSynchronize(A->ctx->s_main));
-  if (nv) HIPC(hipMemcpy(hval.data(), A->d_val, nv * S, hipMemcpyDeviceToHost));
+  if (nv) HIPC(hipMemcpy(hval.data(), A->main.val, nv * S, hipMemcpyDeviceToHost));
   for (int64_t p = 0; p < A->csc_nnz; ++p)
     std::memcpy((unsigned char*)nzval + p * S, &hval[nz_index(A, p) * S], S);
   return 0;
 }
 
 // Matrix exchanger (Interfaces.jl:2312-2372): lids are CSC nz positions k
-// (1-based); they become value indices of d_val.
+// (1-based); they become value indices of main.val.
 int pa_mat_xchg_create(pa_mat* A, int32_t n_rcv, const int32_t* parts_rcv, const int32_t* ptrs_rcv,
                        const int64_t* k_rcv, int32_t n_snd, const int32_t* parts_snd, const int32_t* ptrs_snd,
                        const int64_t* k_snd, pa_xchg** out) {
@@ -3105,7 +3109,7 @@ int pa_mat_exchange_all(int n, pa_mat* const A[], pa_xchg* const xg[], int op, i
     vs[i].ctx = A[i]->ctx;
     vs[i].dtype = A[i]->dtype;
     vs[i].n = nvals(A[i]);
-    vs[i].d = A[i]->d_val;
+    vs[i].d = A[i]->main.val;
     vp[i] = &vs[i];
   }
   if (pa_exchange_all(n, vp.data(), xg, nullptr, op, reverse, 0)) return -1;
@@ -3114,8 +3118,8 @@ int pa_mat_exchange_all(int n, pa_mat* const A[], pa_xchg* const xg[], int op, i
     HIPC(hipSetDevice(c->device));
     if (zero_sent) {
       unsigned char z[16] = {0};
-      if (reverse) launch_fill(A[i]->dtype, xg[i]->n_rcv_data, 0, xg[i]->d_lids_rcv, A[i]->d_val, z, c->s_main);
-      else launch_fill(A[i]->dtype, xg[i]->n_snd_data, 0, xg[i]->d_lids_snd, A[i]->d_val, z, c->s_main);
+      if (reverse) launch_fill(A[i]->dtype, xg[i]->n_rcv_data, 0, xg[i]->d_lids_rcv, A[i]->main.val, z, c->s_main);
+      else launch_fill(A[i]->dtype, xg[i]->n_snd_data, 0, xg[i]->d_lids_snd, A[i]->main.val, z, c->s_main);
     }
     if (refresh_side(A[i], c->s_main)) return -1;
   }
@@ -3127,23 +3131,6 @@ int pa_mat_destroy(pa_mat* A) {
   if (!A) return 0;
   (void)hipSetDevice(A->ctx->device);
   (void)hipStreamSynchronize(A->ctx->s_main);
-  dev_free(A->d_slice_off);
-  dev_free(A->d_slice_len);
-  dev_free(A->d_int_list);
-  dev_free(A->d_bnd_list);
-  dev_free(A->d_col);
-  dev_free(A->d_val);
-  dev_free(A->d_nz_slot);
-  for (void* p : {(void*)A->d_kind, (void*)A->d_plen, (void*)A->d_pdesc, (void*)A->d_pat, (void*)A->d_mask,
-                  (void*)A->d_pint_list, (void*)A->d_pbnd_list, (void*)A->d_xint_list,
-                  (void*)A->d_xbnd_list, (void*)A->d_s_off, (void*)A->d_s_len,
-                  (void*)A->d_s_col, A->d_s_val, (void*)A->d_s_rowmap, (void*)A->d_s_rowlen, A->d_dotp,
-                  (void*)A->d_long_row, (void*)A->d_long_ptr, (void*)A->d_long_col, (void*)A->d_sflags,
-                  (void*)A->d_lmask, (void*)A->d_lchunk_start, (void*)A->d_lrow_chunk, A->d_lpart,
-                  (void*)A->d_col16, (void*)A->d_gbase, (void*)A->d_dint_list, (void*)A->d_dbnd_list})
-    dev_free(p);
-  free_triple_sell(A);
-  free_uniform(A);
   delete A;
   return 0;
 }
@@ -3153,31 +3140,31 @@ int pa_mat_format_info(const pa_mat* A, int64_t* pattern_slices, int64_t* regula
   CHECK_ARG(A, "null matrix");
   if (pattern_slices) *pattern_slices = A->npattern_slices;
   if (regular_rows) *regular_rows = A->nregular_rows;
-  if (side_rows) *side_rows = A->s_nrows;
-  if (side_slots) *side_slots = A->s_slots;
+  if (side_rows) *side_rows = A->side.nrows;
+  if (side_slots) *side_slots = A->side.slots;
   return 0;
 }
 
 int pa_mat_delta16_info(const pa_mat* A, int64_t* delta16_slices) {
   CHECK_ARG(A, "null matrix");
-  if (delta16_slices) *delta16_slices = A->nd_int + A->nd_bnd;
+  if (delta16_slices) *delta16_slices = A->sl_d16.n_int + A->sl_d16.n_bnd;
   return 0;
 }
 
 int pa_mat_pair_info(const pa_mat* A, int64_t* pair_slices, int64_t* pair_rows) {
   CHECK_ARG(A, "null matrix");
-  if (pair_slices) *pair_slices = A->t_pair_slices;
-  if (pair_rows) *pair_rows = A->t_pair_rows;
+  if (pair_slices) *pair_slices = A->tri.pair_slices;
+  if (pair_rows) *pair_rows = A->tri.pair_rows;
   return 0;
 }
 
 int pa_mat_triple_info(const pa_mat* A, int64_t* t_slices, int64_t* t_rows, int64_t* tri_slices,
                        int64_t* tri_rows) {
   CHECK_ARG(A, "null matrix");
-  if (t_slices) *t_slices = A->t_nslices;
-  if (t_rows) *t_rows = A->t_nrows;
-  if (tri_slices) *tri_slices = A->t_tri_slices;
-  if (tri_rows) *tri_rows = A->t_tri_rows;
+  if (t_slices) *t_slices = A->tri.nslices;
+  if (t_rows) *t_rows = A->tri.nrows;
+  if (tri_slices) *tri_slices = A->tri.tri_slices;
+  if (tri_rows) *tri_rows = A->tri.tri_rows;
   return 0;
 }
 
@@ -3193,7 +3180,7 @@ int pa_mat_long_rows(const pa_mat* A, int64_t* n_long, int64_t* n_long_nnz) {
 // metadata (offsets, lengths, lists, patterns, masks, side-row maps).
 int pa_mat_device_ptrs(const pa_mat* A, uint64_t out[8]) {
   CHECK_ARG(A && out, "null argument");
-  const void* p[8] = {A->d_val, A->d_col, A->d_slice_off, A->d_plen, A->d_pat, A->d_mask, A->d_s_val, A->d_s_col};
+  const void* p[8] = {A->main.val, A->main.col, A->main.off, A->d_plen, A->d_pat, A->d_mask, A->side.val, A->side.col};
   for (int i = 0; i < 8; ++i) out[i] = (uint64_t)(uintptr_t)p[i];
   return 0;
 }
@@ -3203,21 +3190,21 @@ int pa_mat_traffic(const pa_mat* A, int64_t* value_bytes, int64_t* index_bytes, 
   TuneScope ts(A->ctx);
   const int64_t S = (int64_t)dtype_size(A->dtype), H = A->H, W = H / 64;
   const bool pat = pattern_layout(A);
-  const bool split = A->d_bnd_list != nullptr;
+  const bool split = A->sl_all.d_bnd != nullptr;
   int64_t v = 0, ix = 0, m = 0;
-  for (int64_t s = 0; s < A->nslices; ++s) {
-    const int kd = pat ? A->h_kind[s] : 0;
-    if (kd == 1) {
+  for (int64_t s = 0; s < A->main.nslices; ++s) {
+    const int kd = pat ? A->h_kind[s] : kBkInt32;
+    if (kd == kBkPattern) {
       // (the uniform layout: the short-row tail launch reads K entries)
-      v += (int64_t)(A->d_uval ? A->uK : A->h_plen[s]) * H * S;
+      v += (int64_t)(A->uni.val ? A->uni.K : A->h_plen[s]) * H * S;
       // mask, offset, length | pattern id, list entry; with SPMV_DESC the
       // descriptor instead (desc_words): counted as the larger
       m += std::max<int64_t>(W * 8 + 8 + 4, 4 * desc_words(A->R)) + 4;
-    } else if (kd == 3) {
+    } else if (kd == kBkDelta16) {
       v += (int64_t)A->h_slen[s] * H * S;
       ix += (int64_t)A->h_slen[s] * H * 2;
       m += 8 + 4 + 4 + 4;  // offset, length, list entry, ghost base
-    } else if (kd == 5) {
+    } else if (kd == kBkMoved) {
       // rows in the triple SELL (below)
     } else {
       v += (int64_t)A->h_slen[s] * H * S;
@@ -3227,12 +3214,12 @@ int pa_mat_traffic(const pa_mat* A, int64_t* value_bytes, int64_t* index_bytes, 
   }
   if (pat) {
     m += A->npatterns * A->kmax * 4;  // the distinct patterns (read once; hot thereafter)
-    v += A->s_slots * S;
-    ix += A->s_slots * 4 + A->s_nrows * 4;  // column ids, row map
-    m += A->s_nslices * 12;
-    v += A->t_slots * S;              // triple SELL: values (padding included)
-    ix += A->t_code_slots * 2 + A->t_nrows * 4;  // codes (one per triple in tri slices), row map
-    m += A->t_nslices * (8 + 4 + 4 + 4);  // offset, length, ghost base, list entry (the 16 B descriptor + list entry)
+    v += A->side.slots * S;
+    ix += A->side.slots * 4 + A->side.nrows * 4;  // column ids, row map
+    m += A->side.nslices * 12;
+    v += A->tri.slots * S;              // triple SELL: values (padding included)
+    ix += A->tri.code_slots * 2 + A->tri.nrows * 4;  // codes (one per triple in tri slices), row map
+    m += A->tri.nslices * (8 + 4 + 4 + 4);  // offset, length, ghost base, list entry (the 16 B descriptor + list entry)
   }
   v += A->n_lnz * S;
   ix += A->n_lnz * 4;
@@ -3246,11 +3233,11 @@ int pa_mat_traffic(const pa_mat* A, int64_t* value_bytes, int64_t* index_bytes, 
 int pa_mat_info(const pa_mat* A, int64_t* nrows, int64_t* nnz, int64_t* slots, int64_t* nslices,
                 int64_t* nslices_int) {
   CHECK_ARG(A, "null matrix");
-  if (nrows) *nrows = A->nrows;
+  if (nrows) *nrows = A->main.nrows;
   if (nnz) *nnz = A->nnz;
-  if (slots) *slots = A->slots;
-  if (nslices) *nslices = A->nslices;
-  if (nslices_int) *nslices_int = A->nslices_int;
+  if (slots) *slots = A->main.slots;
+  if (nslices) *nslices = A->main.nslices;
+  if (nslices_int) *nslices_int = A->sl_all.n_int;
   return 0;
 }
 
@@ -3275,8 +3262,8 @@ struct CGFuse {
 // 0..noids-1: the device CG needs contiguous owned lids), after the halo and
 // before the dot fold (whose α step marks the x update as applied)
 static void cg_ghosts(const CGFuse* fz, int i, const pa_mat* A, const pa_vec* r, hipStream_t st) {
-  if (!fz || r->n <= A->nrows) return;
-  launch_cg_ghost(A->dtype, A->nrows, r->n, r->d, fz->u_old[i], fz->u_new[i], fz->xacc[i], fz->st[i], st);
+  if (!fz || r->n <= A->main.nrows) return;
+  launch_cg_ghost(A->dtype, A->main.nrows, r->n, r->d, fz->u_old[i], fz->u_new[i], fz->xacc[i], fz->st[i], st);
 }
 
 // The slices of a matrix that one phase of a mul! launches: the interior
@@ -3302,26 +3289,23 @@ static SliceList slice_list(const pa_mat* A, SlicePhase phase) {
   SliceList L;
   const bool in = phase != kBoundary, bnd = phase != kInterior;
   if (pattern_layout(A)) {
-    if (in) {
-      L.add(kPattern, A->np_int, A->d_pint_list);
-      L.add(kInt32, A->nx_int, A->d_xint_list);
-      L.add(kDelta16, A->nd_int, A->d_dint_list);
-    }
+    const std::pair<SliceKind, const SliceSet*> sets[] = {
+        {kPattern, &A->sl_pat}, {kInt32, &A->sl_i32}, {kDelta16, &A->sl_d16}};
+    if (in)
+      for (const auto& [k, S] : sets) L.add(k, S->n_int, S->d_int);
     if (bnd) {
-      L.add(kPattern, A->np_bnd, A->d_pbnd_list);
-      L.add(kInt32, A->nx_bnd, A->d_xbnd_list);
-      L.add(kDelta16, A->nd_bnd, A->d_dbnd_list);
-      L.add(kSide, A->s_nslices, nullptr);
+      for (const auto& [k, S] : sets) L.add(k, S->n_bnd, S->d_bnd);
+      L.add(kSide, A->side.nslices, nullptr);
     }
     // the triple SELL: a whole call runs its slices in their own order, without the lists
-    if (phase == kWhole) L.add(kTriple, A->t_nslices, nullptr);
-    else if (in) L.add(kTriple, A->nt_int, A->d_t_int_list);
-    else L.add(kTriple, A->nt_bnd, A->d_t_bnd_list);
-  } else if (A->d_bnd_list) {  // split layout (the interior list may be empty)
-    if (in) L.add(kInt32, A->nslices_int, A->d_int_list);
-    if (bnd) L.add(kInt32, A->nslices - A->nslices_int, A->d_bnd_list);
+    if (phase == kWhole) L.add(kTriple, A->tri.nslices, nullptr);
+    else if (in) L.add(kTriple, A->tri.list.n_int, A->tri.list.d_int);
+    else L.add(kTriple, A->tri.list.n_bnd, A->tri.list.d_bnd);
+  } else if (A->sl_all.d_bnd) {  // split layout (the interior list may be empty)
+    if (in) L.add(kInt32, A->sl_all.n_int, A->sl_all.d_int);
+    if (bnd) L.add(kInt32, A->sl_all.n_bnd, A->sl_all.d_bnd);
   } else if (in) {
-    L.add(kInt32, A->nslices, nullptr);
+    L.add(kInt32, A->main.nslices, nullptr);
   }
   return L;
 }
@@ -3506,8 +3490,8 @@ static int spmv_grouped(const SpmvCall& C, bool direct) {
         if (w.kind == kind) v.push_back(C.part(i, w.nwork, w.list));
     if (side_tail)
       for (int i = 0; i < n; ++i)
-        if (A[i]->s_nslices > 0) {
-          SpmvPart q = C.part(i, A[i]->s_nslices, nullptr);
+        if (A[i]->side.nslices > 0) {
+          SpmvPart q = C.part(i, A[i]->side.nslices, nullptr);
           q.side = true;
           v.push_back(q);
         }
@@ -3516,7 +3500,7 @@ static int spmv_grouped(const SpmvCall& C, bool direct) {
   if (dmark ? mark(2) : mark(0)) return -1;
   int merged = 1;
   bool big_part = false;  // one part alone fills the GPU many times: per-kind launches (knobs().spmv_merge_max)
-  if (knobs().spmv_merge_max > 0 && n == 1) big_part = A[0]->nslices > knobs().spmv_merge_max;
+  if (knobs().spmv_merge_max > 0 && n == 1) big_part = A[0]->main.nslices > knobs().spmv_merge_max;
   // parts of pattern slices and short side rows only, no halo: the per-kind
   // path's side tail is ONE launch too, through the group kernel (its
   // arguments in the kernel's argument segment, no table search per wave):
@@ -3526,9 +3510,9 @@ static int spmv_grouped(const SpmvCall& C, bool direct) {
   bool tail_only = knobs().side_tail && !any_x && !fz && 2 * n <= PA_GROUP_MAX && A[0]->R <= 2;
   for (int i = 0; i < n && tail_only; ++i) {
     const pa_mat* M = A[i];
-    tail_only = pattern_layout(M) && M->np_bnd == 0 && M->nx_int + M->nx_bnd == 0 &&
-                M->nd_int + M->nd_bnd == 0 && M->t_nslices == 0 && M->n_long == 0 &&
-                (M->s_nslices == 0 || M->maxlen_side <= 8);
+    tail_only = pattern_layout(M) && M->sl_pat.n_bnd == 0 && M->sl_i32.n_int + M->sl_i32.n_bnd == 0 &&
+                M->sl_d16.n_int + M->sl_d16.n_bnd == 0 && M->tri.nslices == 0 && M->n_long == 0 &&
+                (M->side.nslices == 0 || M->side.maxlen <= 8);
   }
   if (knobs().spmv_merge && !big_part && !tail_only && (!any_x || direct)) {
     // no halo in flight (none, or pulled already on this stream): every slice
@@ -3564,8 +3548,8 @@ static int spmv_grouped(const SpmvCall& C, bool direct) {
     if (knobs().side_tail && (!any_x || direct) && !fz && 2 * n <= PA_GROUP_MAX) {
       for (int i = 0; i < n; ++i) {
         if (!pattern_layout(A[i])) { side_tailed = false; break; }
-        if (A[i]->s_nslices > 0) {
-          if (A[i]->maxlen_side > 8) { side_tailed = false; break; }
+        if (A[i]->side.nslices > 0) {
+          if (A[i]->side.maxlen > 8) { side_tailed = false; break; }
           side_tailed = true;
         }
       }
@@ -3603,7 +3587,7 @@ static int launch_phase(const SpmvCall& C, SlicePhase phase, int i, hipStream_t 
         W.push_back(k);
       }
   if (E.empty()) return 0;
-  if (E.size() > 1 && knobs().spmv_merge && !(knobs().spmv_merge_max > 0 && A->nslices > knobs().spmv_merge_max)) {
+  if (E.size() > 1 && knobs().spmv_merge && !(knobs().spmv_merge_max > 0 && A->main.nslices > knobs().spmv_merge_max)) {
     const int rc = launch_spmv_merged((int)E.size(), W.data(), E.data(), C.has_alpha, C.bmode, C.alpha, C.beta,
                                       A->ctx, st);
     if (rc < 0) PA_FAIL("mul!: merged launch table (device allocation or copy) failed");
@@ -3727,8 +3711,8 @@ static int spmv_impl(int n, pa_mat* const A[], pa_vec* const y[], const pa_index
         // one partial per main, side and triple-SELL slice and long row;
         // zeroed once: the slices a call does not launch (moved to the
         // triple SELL) add 0 to the fold
-        const int64_t nbp = std::max<int64_t>(dot_base(A[i], kTriple) + A[i]->t_nslices + A[i]->n_long, 1);
-        HIPC(hipMalloc(&A[i]->d_dotp, nbp * 16));
+        const int64_t nbp = std::max<int64_t>(dot_base(A[i], kTriple) + A[i]->tri.nslices + A[i]->n_long, 1);
+        HIPC(A[i]->d_dotp.alloc(nbp * 16));
         HIPC(hipMemset(A[i]->d_dotp, 0, nbp * 16));
       }
       dotp[i] = A[i]->d_dotp;
@@ -3739,7 +3723,7 @@ static int spmv_impl(int n, pa_mat* const A[], pa_vec* const y[], const pa_index
     CHECK_ARG(A[i]->dtype == dt && y[i]->dtype == dt && x[i]->dtype == dt, "mul!: element types differ");
     CHECK_ARG(x[i]->n == A[i]->ncols_lids, "mul!: length(b.values) != num_lids(a.cols) (DimensionMismatch)");
     const pa_index* yi = y_idx ? y_idx[i] : nullptr;
-    CHECK_ARG(yi && yi->noids == A[i]->nrows && yi->nlids == y[i]->n,
+    CHECK_ARG(yi && yi->noids == A[i]->main.nrows && yi->nlids == y[i]->n,
               "mul!: c.rows owned ids differ from a.rows (oids_are_equal)");
     if (x_idx && x_idx[i]) {
       const pa_index* xi = x_idx[i];
@@ -4288,7 +4272,7 @@ int pa_cg_solve_all(int n, pa_mat* const A[], pa_vec* const x[], const pa_vec* c
   bool can_fuse = true;
   // (the fused u update is written by the main structure's waves: not for
   // rows that long-row kernels or the triple SELL compute)
-  for (int i = 0; i < n; ++i) can_fuse = can_fuse && A[i]->n_long == 0 && A[i]->t_nrows == 0;
+  for (int i = 0; i < n; ++i) can_fuse = can_fuse && A[i]->n_long == 0 && A[i]->tri.nrows == 0;
   if (R.remote && knobs().cg_fuse != 0) {  // every rank the same (cg_agree_fuse): RCCL max over the ranks
     pa_ctx* c0 = R.ctxs[0];
     const std::function<int(float*)> red = [&](float* v) -> int {
@@ -4728,30 +4712,23 @@ int pa_mat_stencil(pa_ctx* c, int dtype, int kind, const int64_t gdims[3], const
   const int64_t nrows = box_n[0] * box_n[1] * box_n[2];
   CHECK_ARG(nrows < (int64_t)INT32_MAX && nlids_cols >= nrows && nlids_cols < (int64_t)INT32_MAX, "sizes");
   HIPC(hipSetDevice(c->device));
-  pa_mat* A = new pa_mat();
-  A->ctx = c;
-  A->dtype = dtype;
-  A->R = sell_rows_per_lane(dtype);
-  A->H = 64 * A->R;
-  A->nrows = nrows;
-  A->ncols_lids = nlids_cols;
+  std::unique_ptr<pa_mat> A = mat_start(c, dtype, nrows, nlids_cols);
   StencilGeom g;
   for (int d = 0; d < 3; ++d) { g.N[d] = gdims[d]; g.lo[d] = box_lo[d]; g.n[d] = box_n[d]; }
   g.kind = kind;
   const int64_t ns = (nrows + A->H - 1) / A->H;
   const int64_t ext = (box_n[0] + 2) * (box_n[1] + 2) * (box_n[2] + 2);
-  int32_t *d_shell = nullptr, *d_slen = nullptr, *d_sg = nullptr, *d_err = nullptr;
-  double* d_coef = nullptr;
-  auto cleanup = [&]() { dev_free(d_shell); dev_free(d_slen); dev_free(d_sg); dev_free(d_err); dev_free(d_coef); };
+  DevBuf<int32_t> d_shell, d_slen, d_sg, d_err;
+  DevBuf<double> d_coef;
   if (shell_lid) {
-    HIPC(hipMalloc((void**)&d_shell, ext * 4));
+    HIPC(d_shell.alloc(ext));
     HIPC(hipMemcpy(d_shell, shell_lid, ext * 4, hipMemcpyHostToDevice));
   }
-  HIPC(hipMalloc((void**)&d_coef, ncoeffs * 8));
+  HIPC(d_coef.alloc(ncoeffs));
   HIPC(hipMemcpy(d_coef, coeffs, ncoeffs * 8, hipMemcpyHostToDevice));
-  HIPC(hipMalloc((void**)&d_slen, std::max<int64_t>(ns, 1) * 4));
-  HIPC(hipMalloc((void**)&d_sg, std::max<int64_t>(ns, 1) * 4));
-  HIPC(hipMalloc((void**)&d_err, 4));
+  HIPC(d_slen.alloc(std::max<int64_t>(ns, 1)));
+  HIPC(d_sg.alloc(std::max<int64_t>(ns, 1)));
+  HIPC(d_err.alloc(1));
   // zeroed on the compute stream the kernels below run on (a hipMemset on
   // the null stream is not ordered before work on a non-blocking stream)
   HIPC(hipMemsetAsync(d_slen, 0, std::max<int64_t>(ns, 1) * 4, c->s_main));
@@ -4765,33 +4742,32 @@ int pa_mat_stencil(pa_ctx* c, int dtype, int kind, const int64_t gdims[3], const
   HIPC(hipMemcpy(slen.data(), d_slen, ns * 4, hipMemcpyDeviceToHost));
   HIPC(hipMemcpy(sg.data(), d_sg, ns * 4, hipMemcpyDeviceToHost));
   HIPC(hipMemcpy(&herr, d_err, 4, hipMemcpyDeviceToHost));
-  if (herr) { cleanup(); delete A; PA_FAIL("stencil: a neighbour inside the domain has no lid (ghost shell table incomplete)"); }
+  CHECK_ARG(!herr, "stencil: a neighbour inside the domain has no lid (ghost shell table incomplete)");
   std::vector<char> sghost(ns);
   for (int64_t s = 0; s < ns; ++s) sghost[s] = sg[s] != 0;
-  if (finish_sell_layout(A, slen, sghost, nullptr)) { cleanup(); pa_mat_destroy(A); return -1; }
+  if (finish_sell_layout(A.get(), slen, sghost, nullptr)) return -1;
   const size_t S = dtype_size(dtype);
-  int64_t nnz_owned = 0;
-  (void)nnz_owned;
-  hipError_t e1 = hipMalloc((void**)&A->d_col, std::max<int64_t>(A->slots, 1) * 4);
+  const hipError_t e1 = A->main.col.alloc(std::max<int64_t>(A->main.slots, 1));
   hipError_t e2 = hipErrorMemoryAllocation;
   // PA_DIAG_VAL_CONTIGUOUS (placement diagnostics only, tools/placement_pmc.py,
   // DESIGN.md §4.1): the values in physically contiguous memory when the
   // driver can provide it
   if (std::getenv("PA_DIAG_VAL_CONTIGUOUS")) {
-    e2 = hipExtMallocWithFlags(&A->d_val, std::max<int64_t>(A->slots, 1) * S, hipDeviceMallocContiguous);
-    if (e2 != hipSuccess)
+    void* pv = nullptr;
+    e2 = hipExtMallocWithFlags(&pv, std::max<int64_t>(A->main.slots, 1) * S, hipDeviceMallocContiguous);
+    if (e2 == hipSuccess) A->main.val.adopt(pv);
+    else
       std::fprintf(stderr, "PA_DIAG_VAL_CONTIGUOUS: contiguous allocation of %lld B failed (%s): hipMalloc\n",
-                   (long long)(std::max<int64_t>(A->slots, 1) * S), hipGetErrorString(e2));
+                   (long long)(std::max<int64_t>(A->main.slots, 1) * S), hipGetErrorString(e2));
   }
   if (e2 != hipSuccess) {
     (void)hipGetLastError();
-    e2 = hipMalloc(&A->d_val, std::max<int64_t>(A->slots, 1) * S);
+    e2 = A->main.val.alloc(std::max<int64_t>(A->main.slots, 1) * S);
   }
-  if (e1 != hipSuccess || e2 != hipSuccess) { cleanup(); pa_mat_destroy(A); PA_FAIL("hipMalloc(matrix) failed: out of device memory"); }
-  launch_stencil_fill(g, d_shell, d_coef, nrows, (int)nrows, A, d_err, c->s_main);
+  CHECK_ARG(e1 == hipSuccess && e2 == hipSuccess, "hipMalloc(matrix) failed: out of device memory");
+  launch_stencil_fill(g, d_shell, d_coef, nrows, (int)nrows, A.get(), d_err, c->s_main);
   HIPC(hipGetLastError());
   HIPC(hipStreamSynchronize(c->s_main));
-  cleanup();
   // owned nnz: count from the structure (interior rows kind, boundary 1)
   int64_t nnz = 0;
   {
@@ -4804,13 +4780,7 @@ int pa_mat_stencil(pa_ctx* c, int dtype, int kind, const int64_t gdims[3], const
     nnz = inner * kind + (nrows - inner);
   }
   A->nnz = nnz;
-  {
-    int kmax = 0;
-    for (int32_t l : slen) kmax = std::max(kmax, l);
-    if (finalize_pattern(A, kmax, nrows, false)) { pa_mat_destroy(A); return -1; }
-  }
-  *out = A;
-  return 0;
+  return mat_finish(A, slen, nrows, true, nullptr, out);
 }
 
 }  // extern "C"

@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/pa_hip.h"
@@ -226,9 +227,9 @@ struct CGState {
 // Grouped launches (parts of one process sharing a stream pair): one launch
 // per phase covers up to PA_GROUP_MAX parts (kernel-argument tables).
 constexpr int PA_GROUP_MAX = 8;
-constexpr int32_t kTriSlice = 1 << 30;  // pa_mat::d_t_len: a triple slice
-constexpr int32_t kTriPair = 1 << 29;   // pa_mat::d_t_len: a pair slice (lane l: rows a_l, a_l + 1; build_triple_sell)
-constexpr int32_t kTriLen = kTriPair - 1;  // pa_mat::d_t_len: the entries per row
+constexpr int32_t kTriSlice = 1 << 30;  // TripleSell::len: a triple slice
+constexpr int32_t kTriPair = 1 << 29;   // TripleSell::len: a pair slice (lane l: rows a_l, a_l + 1; build_triple_sell)
+constexpr int32_t kTriLen = kTriPair - 1;  // TripleSell::len: the entries per row
 // The slice kinds of a mul!: which of a pa_mat's structures
 // and column encodings a launch entry runs.  kind_desc (pa_spmv.hip) holds
 // what each kind reads; slice_list (pa_api.cpp) a matrix's entries per phase.
@@ -449,11 +450,6 @@ struct pa_pull {
   int32_t* d_bid = nullptr;
   int64_t* d_elem = nullptr;
   void** d_bases = nullptr;
-  // host copies: a graph capture gives the graph its own device copies
-  // (the cached tables may be rebuilt while the graph still replays)
-  std::vector<int32_t> h_bid;
-  std::vector<int64_t> h_elem;
-  std::vector<void*> h_bases;
 };
 
 struct pa_xchg {
@@ -510,58 +506,155 @@ struct pa_vec {
 // 4 header words + the slice's H/64 64-bit mask words, a power of two
 constexpr int desc_words(int R) { return R <= 2 ? 8 : 16; }
 
+namespace pa {
+// A device array and its owner (move-only).  It converts to its pointer, so
+// launches and copies take it as they would the raw pointer.
+template <typename T>
+struct DevBuf {
+  T* p = nullptr;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) adopt(o.p), o.p = nullptr;
+    return *this;
+  }
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { reset(); }
+  void reset() { adopt(nullptr); }
+  void adopt(T* q) {  // takes over an allocation of the HIP allocator
+    if (p) (void)hipFree(p);
+    p = q;
+  }
+  hipError_t alloc(size_t n) {  // n elements (bytes for DevBuf<void>), uninitialised
+    reset();
+    return hipMalloc((void**)&p, n * sizeof(std::conditional_t<std::is_void<T>::value, char, T>));
+  }
+  template <typename U>
+  hipError_t upload(const std::vector<U>& h) {  // an empty vector leaves the buffer null
+    static_assert(std::is_same<U, T>::value, "element type");
+    reset();
+    if (h.empty()) return hipSuccess;
+    const hipError_t e = alloc(h.size());
+    return e != hipSuccess ? e : hipMemcpy(p, h.data(), h.size() * sizeof(U), hipMemcpyHostToDevice);
+  }
+  operator T*() const { return p; }
+  template <typename U>
+  explicit operator U*() const { return (U*)p; }
+};
+// n elements of a device array into h, on st (the caller synchronises)
+template <typename T>
+inline hipError_t download(std::vector<T>& h, const T* d, size_t n, hipStream_t st) {
+  h.resize(n);
+  return hipMemcpyAsync(h.data(), d, n * sizeof(T), hipMemcpyDeviceToHost, st);
+}
+
+// The kind of a slice of the main structure as the build records it
+// (pa_mat::h_kind, pa_mat::d_kind; k_pattern_detect, k_delta16 and k_u_fill
+// write and read the numbers).  The device copy holds kBkInt32, kBkPattern
+// and kBkDelta16 only: a delta16 slice whose rows moved to the triple SELL
+// stays kBkDelta16 there (spmv_format 0 still runs it, and reads its
+// interleaved Float32 layout from that value) and is kBkMoved on the host.
+enum BuildKind : int32_t { kBkInt32 = 0, kBkPattern = 1, kBkDelta16 = 3, kBkMoved = 5 };
+
+// One sliced-ELL structure: slice s holds rows [s*H, (s+1)*H) of the
+// structure in len[s] entries per row at slot offset off[s].
+struct Sell {
+  int64_t nrows = 0, nslices = 0;
+  int64_t slots = 0;          // incl. padding
+  int maxlen = INT32_MAX;     // longest row (SH kernels when <= 8)
+  DevBuf<int64_t> off;        // nslices
+  DevBuf<int32_t> len;        // nslices (entries per row, max over the slice)
+  DevBuf<int32_t> col;        // slots: x lid (0-based) or -1 padding
+  DevBuf<uint16_t> col16;     // slots: 16-bit codes (delta16 slices, triple SELL)
+  DevBuf<int32_t> gbase;      // per slice: smallest ghost column (base of the ghost codes)
+  DevBuf<void> val;           // slots (the main structure: then the ghost-row and long-row values)
+  DevBuf<int32_t> rowmap;     // structure row -> oid (null: the identity)
+  DevBuf<int32_t> rowlen;     // structure row -> its entries
+};
+// The slices of one kind by phase: without ghost reads (before the halo) and with
+struct SliceSet {
+  int64_t n_int = 0, n_bnd = 0;
+  DevBuf<int32_t> d_int, d_bnd;
+};
+// Triple SELL (pa_tune "spmv_tri16"): the rows of the
+// delta16 slices, re-sliced by class — rows whose column list is
+// consecutive triples (c, c+1, c+2) first, then the other rows, each class
+// by length (descending) and oid — with a row map.  A "tri" slice (every
+// row regular, length % 3 == 0) keeps one 16-bit code per triple and its
+// lane reads a triple's x as one run; the other slices keep one code per
+// entry.  Rows of a slice are interleaved (row i at lane i % 64, position
+// i / 64).  Values are copies of the main slots (refreshed with the side
+// SELL); the main delta16 slices are not launched then (kBkMoved).
+// len: entries per row, bit 30: tri slice (kTriSlice), bit 29: pair slice;
+// col16: tri slices one code per triple (slot groups 0..len/3-1);
+// val: lane-major packs of R like the main SELL (pack: tri slices per triple)
+struct TripleSell : Sell {
+  SliceSet list;
+  DevBuf<int64_t> src;        // structure row -> its main-layout slot of entry 0 (entry k: + k*64*R)
+  DevBuf<int32_t> desc;       // per slice {offset / H, len, gbase, 0} (SPMV_DESC)
+  int pack = 0;               // slices of 2 rows per lane (spmv_tri_pack): bit 2 pair slices; bit 0 (Float32)
+                              // a pair slice's triple t as {entries 0,1 x R rows} 16 B + {entry 2} 8 B per lane
+  int64_t tri_slices = 0, tri_rows = 0, code_slots = 0;
+  int64_t pair_slices = 0, pair_rows = 0;  // pair slices and the rows they hold
+  std::vector<int32_t> h_len;  // host copy for pa_mat_traffic
+};
+// the uniform layout of short pattern rows (build_uniform): K = |U| <= 7
+// entries per row at slice * H * K, U's offsets, pattern id -> U position
+struct UniformRows {
+  DevBuf<void> val;
+  DevBuf<int32_t> emap;
+  int K = 0;
+  int32_t pat[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+};
+}  // namespace pa
+
 struct pa_mat {
   pa_ctx* ctx = nullptr;
   int dtype = PA_F64;
   int cg_fuse_choice = -1;   // device CG with cg_fuse 2 (auto): the faster u-update variant measured on this matrix
   int R = 2;                 // rows per lane
   int H = 128;               // rows per slice = 64*R
-  int64_t nrows = 0;         // owned rows
   int64_t ncols_lids = 0;    // x length expected
   int64_t nnz = 0;           // owned-row nonzeros
-  int64_t slots = 0;         // SELL slots incl. padding
-  int64_t nslices = 0;
-  int64_t nslices_int = 0;   // slices without ghost-column entries
   bool csr = false;          // built from a SparseMatrixCSR: α scales each product, (v*x)*α (SparseUtils.jl:247)
-  std::vector<int32_t> h_slen;      // host copies for pa_mat_traffic: int32-layout slice lengths,
-  std::vector<int32_t> h_kind;      // pattern-layout slice kinds (0 int32, 1 pattern, 3 delta16)
-  std::vector<int32_t> h_plen;      // and entries per row of each pattern-layout slice
-  // longest row of each launch kind (SH kernels when <= 8): pattern slices,
-  // int32 slices (of the current encoding), side SELL
-  int maxlen_all = INT32_MAX, maxlen_pm_int = INT32_MAX, maxlen_pat = INT32_MAX, maxlen_side = INT32_MAX;
-  int64_t* d_slice_off = nullptr;   // nslices (slot offset of each slice)
-  int32_t* d_slice_len = nullptr;   // nslices (entries per row, max over slice)
-  int32_t* d_int_list = nullptr;    // interior slice ids (null: all interior 0..n-1)
-  int32_t* d_bnd_list = nullptr;    // boundary slice ids
-  int32_t* d_col = nullptr;         // slots, x lid (0-based) or -1 padding
-  void* d_val = nullptr;            // slots, then n_gnz ghost-row values
+  // The main structure: the owned rows (nrows) in int32 columns; sl_all its
+  // slices without / with ghost-column entries (d_bnd null: no boundary
+  // slice, one launch over 0..nslices-1).  main.col16 / main.gbase: the
+  // delta16 slices (below).  main.val continues past the slots (n_gnz, n_lnz).
+  pa::Sell main;
+  pa::SliceSet sl_all;
+  // host copies for pa_mat_traffic and the build: int32-layout slice lengths,
+  // pattern-layout slice kinds (BuildKind), entries per row of each
+  // pattern-layout slice
+  std::vector<int32_t> h_slen, h_kind, h_plen;
   // CSC nz p → its value: main slot (>= 0) or ghost-row value g (-(g+1)).
   // The ghost rows' nonzeros (stored by FE assembly, never multiplied) sit
-  // after the SELL slots in d_val: the nz exchange/assemble (matrix
+  // after the SELL slots in main.val: the nz exchange/assemble (matrix
   // exchanger, Interfaces.jl:2312-2404) addresses both through one index.
   // Built by pa_mat_from_coo, the map stays on the device (d_nz_slot) until
   // a call that needs it on the host (set/get values, matrix exchanger).
   std::vector<int64_t> h_nz_slot;
-  int64_t* d_nz_slot = nullptr;
+  pa::DevBuf<int64_t> d_nz_slot;
   bool nz_map = false;              // built from a CSC pattern
   int64_t csc_nnz = 0;
   int64_t n_gnz = 0;
-  // long rows (row-length histogram): their own CSR, values in d_val at
+  // long rows (row-length histogram): their own CSR, values in main.val at
   // long_off = slots + n_gnz; CSC nz of a long row: h_nz_slot = -(n_gnz+t+1)
   int64_t n_long = 0, n_lnz = 0, long_off = 0;
-  int32_t* d_long_row = nullptr;     // oids, ascending
-  int64_t* d_long_ptr = nullptr;     // n_long+1
-  int32_t* d_long_col = nullptr;     // x lids, reference order per row
-  int32_t* d_sflags = nullptr;       // per slice: 1 if it holds long rows (int32 path skips them)
-  uint64_t* d_lmask = nullptr;       // nslices*(H/64) bits: long rows
+  pa::DevBuf<int32_t> d_long_row;    // oids, ascending
+  pa::DevBuf<int64_t> d_long_ptr;    // n_long+1
+  pa::DevBuf<int32_t> d_long_col;    // x lids, reference order per row
+  pa::DevBuf<int32_t> d_sflags;      // per slice: 1 if it holds long rows (int32 path skips them)
+  pa::DevBuf<uint64_t> d_lmask;      // nslices*(H/64) bits: long rows
   std::vector<int32_t> h_long_rows;  // sorted oids (excluded from the side SELL)
   // chunks of the long rows (long_rows_exact = 0): chunk c covers long-CSR
   // entries [lchunk_start[c], lchunk_start[c+1]); row i owns chunks
   // [lrow_chunk[i], lrow_chunk[i+1]); one partial per chunk in d_lpart
   int64_t n_lchunks = 0;
-  int64_t* d_lchunk_start = nullptr;
-  int64_t* d_lrow_chunk = nullptr;
-  void* d_lpart = nullptr;
+  pa::DevBuf<int64_t> d_lchunk_start;
+  pa::DevBuf<int64_t> d_lrow_chunk;
+  pa::DevBuf<void> d_lpart;
 
   // Pattern slices (implied columns): in a pattern slice the
   // rows whose column sequence is `row + pat[k]` (k < plen) are "regular"
@@ -569,74 +662,29 @@ struct pa_mat {
   // computed from the side SELL below.  Values keep their int32-SELL slots.
   bool has_pat = false;
   int kmax = 0;                      // pattern stride per slice
-  int32_t* d_kind = nullptr;         // per slice: 1 pattern, 0 int32 columns
-  int32_t* d_pdesc = nullptr;        // per slice desc_words(R) int32: {offset / H, d_plen, 0, 0, mask words} (SPMV_DESC)
-  int32_t* d_plen = nullptr;         // per slice: entries per row (int32 len; pattern slices: len (bits 0-7) | tri flag (bit 8) | pattern id << 9)
-  int32_t* d_pat = nullptr;          // npatterns*kmax offsets: the distinct patterns (dedup_patterns)
+  pa::DevBuf<int32_t> d_kind;        // per slice: its BuildKind (the values the device copy holds: see the enum)
+  pa::DevBuf<int32_t> d_pdesc;       // per slice desc_words(R) int32: {offset / H, d_plen, 0, 0, mask words} (SPMV_DESC)
+  pa::DevBuf<int32_t> d_plen;        // per slice: entries per row (int32 len; pattern slices: len (bits 0-7) | tri flag (bit 8) | pattern id << 9)
+  pa::DevBuf<int32_t> d_pat;         // npatterns*kmax offsets: the distinct patterns (dedup_patterns)
   int64_t npatterns = 0;
   // XCD run length of this matrix's per-kind launches in spmv_xcd_chunk's
   // auto mode (dedup_patterns: the pattern's reach in blocks / 8), 0 = none
   int xcd_auto = 0;
-  uint64_t* d_mask = nullptr;        // nslices*(H/64) regular-row bits
-  int32_t* d_pint_list = nullptr;    // pattern mode: pattern slices without ghost reads
-  int32_t* d_pbnd_list = nullptr;    // pattern mode: pattern slices reading ghosts
-  int64_t np_int = 0, np_bnd = 0;
-  int32_t* d_xint_list = nullptr;    // pattern mode: int32-column slices without ghost columns
-  int32_t* d_xbnd_list = nullptr;    // pattern mode: int32-column slices with ghost columns
-  int64_t nx_int = 0, nx_bnd = 0;
+  pa::DevBuf<uint64_t> d_mask;       // nslices*(H/64) regular-row bits
   int64_t npattern_slices = 0, nregular_rows = 0;
-  // delta16 slices (kind 3): int32-column slices whose columns all fit a
-  // 16-bit code (pa_tune "spmv_delta16"): an owned column c of row r as
-  // c - r in 15 signed bits, a ghost column as the slice's ghost base +
-  // 15 unsigned bits (bit 15 set), 0xFFFF padding — 2 B per slot instead of 4
-  uint16_t* d_col16 = nullptr;       // slots (codes of the delta16 slices)
-  int32_t* d_gbase = nullptr;        // per slice: smallest ghost column
-  int32_t* d_dint_list = nullptr;    // delta16 slices without ghost columns
-  int32_t* d_dbnd_list = nullptr;    // delta16 slices with ghost columns
-  int64_t nd_int = 0, nd_bnd = 0;
-  int maxlen_d16 = INT32_MAX;
-  // side SELL: the irregular rows of pattern slices (row map → oid)
-  int64_t s_nrows = 0, s_nslices = 0, s_slots = 0;
-  int64_t* d_s_off = nullptr;
-  int32_t* d_s_len = nullptr;
-  int32_t* d_s_col = nullptr;
-  void* d_s_val = nullptr;
-  int32_t* d_s_rowmap = nullptr;
-  int32_t* d_s_rowlen = nullptr;
-  // Triple SELL (pa_tune "spmv_tri16"): the rows of the
-  // delta16 slices, re-sliced by class — rows whose column list is
-  // consecutive triples (c, c+1, c+2) first, then the other rows, each class
-  // by length (descending) and oid — with a row map.  A "tri" slice (every
-  // row regular, length % 3 == 0) keeps one 16-bit code per triple and its
-  // lane reads a triple's x as one run; the other slices keep one code per
-  // entry.  Rows of a slice are interleaved (row i at lane i % 64, position
-  // i / 64).  Values are copies of the main slots (refreshed with the side
-  // SELL); the main delta16 slices are not launched then (host kind 5).
-  int64_t t_nrows = 0, t_nslices = 0, t_slots = 0, t_tri_slices = 0, t_tri_rows = 0, t_code_slots = 0;
-  int64_t* d_t_off = nullptr;        // slot offset per slice
-  int32_t* d_t_len = nullptr;        // entries per row (max over the slice), bit 30: tri slice (kTriSlice), bit 29: pair slice
-  uint16_t* d_t_col16 = nullptr;     // codes (tri slices: one per triple, slot groups 0..len/3-1)
-  void* d_t_val = nullptr;           // values (lane-major packs of R, like the main SELL; t_pack: tri slices per triple)
-  int t_pack = 0;                    // slices of 2 rows per lane (spmv_tri_pack): bit 2 pair slices; bit 0 (Float32)
-                                     // a pair slice's triple t as {entries 0,1 × R rows} 16 B + {entry 2} 8 B per lane
-  int64_t t_pair_slices = 0, t_pair_rows = 0;  // pair slices and the rows they hold
-  // the uniform layout of short pattern rows (build_uniform): K = |U| <= 7
-  // entries per row at slice * H * K, U's offsets, pattern id -> U position
-  void* d_uval = nullptr;
-  int32_t* d_uemap = nullptr;
-  int uK = 0;
-  int32_t upat[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  int32_t* d_t_gbase = nullptr;      // per slice: smallest ghost column
-  int32_t* d_t_desc = nullptr;       // per slice {offset / H, d_t_len, d_t_gbase, 0} (SPMV_DESC)
-  int32_t* d_t_rowmap = nullptr;     // structure row → oid
-  int64_t* d_t_src = nullptr;        // structure row → its main-layout slot of entry 0 (entry k: + k*64*R)
-  int32_t* d_t_rowlen = nullptr;     // structure row → its entries
-  int32_t* d_t_int_list = nullptr;   // slices without ghost reads
-  int32_t* d_t_bnd_list = nullptr;   // slices reading ghosts
-  int64_t nt_int = 0, nt_bnd = 0;
-  int maxlen_t = INT32_MAX;
-  std::vector<int32_t> h_t_len;      // host copies for pa_mat_traffic
-  void* d_dotp = nullptr;            // fused dot: one partial per (main + side + triple) slice and long row
+  // the pattern layout's slices of the main structure by kind: pattern
+  // slices, int32-column slices, and delta16 slices — int32-column slices
+  // whose columns all fit a 16-bit code (pa_tune "spmv_delta16"): an owned
+  // column c of row r as c - r in 15 signed bits, a ghost column as the
+  // slice's ghost base + 15 unsigned bits (bit 15 set), 0xFFFF padding — 2 B
+  // per slot instead of 4
+  pa::SliceSet sl_pat, sl_i32, sl_d16;
+  // longest row of each of those kinds (main.maxlen: of all slices)
+  int maxlen_pat = INT32_MAX, maxlen_pm_int = INT32_MAX, maxlen_d16 = INT32_MAX;
+  pa::Sell side;        // the irregular rows of pattern slices (row map → oid), int32 columns
+  pa::TripleSell tri;
+  pa::UniformRows uni;
+  pa::DevBuf<void> d_dotp;  // fused dot: one partial per (main + side + triple) slice and long row
 };
 
 namespace pa {
@@ -649,9 +697,9 @@ inline bool pattern_layout(const pa_mat* A) { return knobs().spmv_format == 1 &&
 // The kernels (SpmvArgs::dot_base) and the fold (SpmvCall::finish_part) both
 // take the bases from here.
 inline int64_t dot_base(const pa_mat* A, SliceKind k) {
-  return k == kSide ? A->nslices : k == kTriple ? A->nslices + A->s_nslices : 0;
+  return k == kSide ? A->main.nslices : k == kTriple ? A->main.nslices + A->side.nslices : 0;
 }
 inline int64_t long_dot_base(const pa_mat* A) {
-  return pattern_layout(A) ? dot_base(A, kTriple) + A->t_nslices : A->nslices;
+  return pattern_layout(A) ? dot_base(A, kTriple) + A->tri.nslices : A->main.nslices;
 }
 }  // namespace pa

@@ -686,10 +686,10 @@ static void stencil_fill_t(const StencilGeom& g, const int32_t* shell, const dou
   const int64_t blocks = (nrows + 255) / 256;
   if (blocks == 0) return;
   hipLaunchKernelGGL((k_stencil_fill<T, R>), dim3(blocks), dim3(256), 0, st, g, shell, coef, nrows,
-                     noids, A->d_slice_off, A->d_slice_len, A->d_col, (T*)A->d_val, err);
-  if (A->nslices > 0 && nrows % (64 * R) != 0)
-    hipLaunchKernelGGL((k_sell_pad_tail<T, R>), dim3(1), dim3(256), 0, st, nrows, A->nslices,
-                       A->d_slice_off, A->d_slice_len, A->d_col, (T*)A->d_val);
+                     noids, A->main.off, A->main.len, A->main.col, (T*)A->main.val, err);
+  if (A->main.nslices > 0 && nrows % (64 * R) != 0)
+    hipLaunchKernelGGL((k_sell_pad_tail<T, R>), dim3(1), dim3(256), 0, st, nrows, A->main.nslices,
+                       A->main.off, A->main.len, A->main.col, (T*)A->main.val);
 }
 
 void launch_stencil_fill(const StencilGeom& g, const int32_t* shell, const double* coef,

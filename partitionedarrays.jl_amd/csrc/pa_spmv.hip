@@ -56,7 +56,7 @@ struct alignas(2 * R) S16Pack {
 enum { SPMV_NT = 1, SPMV_DESC = 2 /* pattern / triple-SELL slices: one descriptor load (make_args) */, SPMV_XPAIR = 4, SPMV_TAILB = 8, SPMV_IDLIST = 16, SPMV_YNT = 32, SPMV_SHORT = 64,
        SPMV_SHORT7 = 128 /* Float64 rows <= 7 entries: k_spmv_group_short7 */,
        SPMV_PRODA = 256 /* per matrix: CSR parent, α scales the product */,
-       SPMV_TPACK = 512 /* per matrix: Float32 pair slices with per-triple value packs (pa_mat::t_pack bit 0) */ };
+       SPMV_TPACK = 512 /* per matrix: Float32 pair slices with per-triple value packs (TripleSell::pack bit 0) */ };
 
 typedef unsigned int spmv_u32x4 __attribute__((ext_vector_type(4)));
 // Process-wide knobs (pa_tune).  Defaults from the A/Bs in
@@ -135,7 +135,7 @@ struct SpmvArgs {
   const PA_GLB uint16_t* col16;
   const PA_GLB int32_t* gbase;
   // int32-column launches over delta16 slices (spmv_format 0): the slices'
-  // kinds; kind 3 = interleaved rows (null: every slice blocked)
+  // kinds; kBkDelta16 = interleaved rows (null: every slice blocked)
   const PA_GLB int32_t* ilv;
   // the device CG's fused u update (XV kernels, pa_cg_solve_all): x is r,
   // the gathered values are u_new = r .+ β.*u_old (β = res²/prev² of cg);
@@ -972,7 +972,7 @@ __device__ __forceinline__ void spmv_wave(const SpmvArgs<T>& a, const int64_t w)
   bool il = false;
   if constexpr (PK == 3) il = kInterleaveD16<R>;
   if constexpr (PK == 4) il = true;
-  if constexpr (PK == 0 && kInterleaveD16<R>) il = a.ilv && a.ilv[s] == 3;
+  if constexpr (PK == 0 && kInterleaveD16<R>) il = a.ilv && a.ilv[s] == kBkDelta16;
   const int rs = il ? 64 : 1;
   const int64_t row0 = s * H + (il ? (int64_t)lane : (int64_t)lane * R);  // the lane's first row
   XSrc<T, XV> xs;
@@ -1108,7 +1108,7 @@ __device__ __forceinline__ void spmv_wave(const SpmvArgs<T>& a, const int64_t w)
       bool packed = false;
       if constexpr (R == 2) {
         // pair slices, per-triple value packs (Float32) and/or batch code
-        // packs (k_t_fill, pa_mat::t_pack), non-temporal
+        // packs (k_t_fill, TripleSell::pack), non-temporal
         using XS = XSrc<T, XV>;
         const bool tp = sizeof(T) == 4 && (a.flags & SPMV_TPACK);
         packed = true;
@@ -1461,43 +1461,34 @@ static void launch_t(const SpmvArgs<T>& a, hipStream_t st) {
     hipLaunchKernelGGL((k_spmv_sell<T, R, ALPHA, BMODE, 8, PAT>), dim3(blocks), dim3(256), 0, st, a);
 }
 
-// What the launches of one slice kind read from a matrix: its structure, the
-// kernels' column encoding, the longest row, where its partials of the fused
-// dot start, and whether a list of all nslices ids may be dropped (the lists
-// of the main structure are ascending subsets of 0..nslices-1)
+// What the launches of one slice kind read from a matrix: its structure
+// and what the kind changes about it — the kernels' column encoding (codes:
+// 16-bit codes and ghost bases instead of int32 columns), the longest row,
+// the slice lengths (pattern slices: the packed length word), where its
+// partials of the fused dot start, and whether a list of all nslices ids may
+// be dropped (the lists of the main structure are ascending subsets of
+// 0..nslices-1)
 struct KindDesc {
+  const Sell* S;
   int pk;
+  bool codes;
   bool idlist;
   int maxlen;
-  int64_t dot_base;
-  const int64_t* soff;
   const int32_t* slen;
-  const int32_t* col;
-  const uint16_t* col16;
-  const int32_t* gbase;
-  const void* val;
-  const int32_t* rowmap;
-  int64_t nrows;
+  int64_t dot_base;
 };
 
 static KindDesc kind_desc(SliceKind k, const pa_mat* A) {
+  const int64_t db = dot_base(A, k);
   switch (k) {
-    case kPattern:
-      return {kPkPattern, true, A->maxlen_pat, 0, A->d_slice_off, A->d_plen, A->d_col, nullptr, nullptr, A->d_val,
-              nullptr, A->nrows};
-    case kDelta16:
-      return {kPkDelta16, true, A->maxlen_d16, 0, A->d_slice_off, A->d_slice_len, A->d_col, A->d_col16, A->d_gbase,
-              A->d_val, nullptr, A->nrows};
-    case kSide:
-      return {kPkInt32, false, A->maxlen_side, dot_base(A, kSide), A->d_s_off, A->d_s_len, A->d_s_col, nullptr,
-              nullptr, A->d_s_val, A->d_s_rowmap, A->s_nrows};
+    case kPattern: return {&A->main, kPkPattern, false, true, A->maxlen_pat, A->d_plen, db};
+    case kDelta16: return {&A->main, kPkDelta16, true, true, A->maxlen_d16, A->main.len, db};
+    case kSide: return {&A->side, kPkInt32, false, false, A->side.maxlen, A->side.len, db};
     case kTriple:  // maxlen >= 9: never the short-row kernels (merged_wave)
-      return {kPkTriple, false, std::max(A->maxlen_t, 9), dot_base(A, kTriple), A->d_t_off, A->d_t_len, nullptr,
-              A->d_t_col16, A->d_t_gbase, A->d_t_val, A->d_t_rowmap, A->t_nrows};
+      return {&A->tri, kPkTriple, true, false, std::max(A->tri.maxlen, 9), A->tri.len, db};
     case kInt32: break;
   }
-  return {kPkInt32, true, pattern_layout(A) ? A->maxlen_pm_int : A->maxlen_all, 0, A->d_slice_off, A->d_slice_len,
-          A->d_col, nullptr, nullptr, A->d_val, nullptr, A->nrows};
+  return {&A->main, kPkInt32, false, true, pattern_layout(A) ? A->maxlen_pm_int : A->main.maxlen, A->main.len, db};
 }
 
 // the kernel arguments of part q's slices of kind k
@@ -1517,7 +1508,7 @@ static SpmvArgs<T> make_args(SliceKind k, const SpmvPart& q, const void* alpha, 
   a.dot_base = d.dot_base;
   a.nwork = q.nwork;
   // every slice of the structure: without the list, one dependent load less per wave
-  const bool all = (knobs().spmv_flags & SPMV_IDLIST) && d.idlist && q.nwork == A->nslices;
+  const bool all = (knobs().spmv_flags & SPMV_IDLIST) && d.idlist && q.nwork == A->main.nslices;
   a.list = (decltype(a.list))(all ? nullptr : q.list);
   a.x = (decltype(a.x))((const T*)q.x);
   a.nx = A->ncols_lids;
@@ -1525,34 +1516,35 @@ static SpmvArgs<T> make_args(SliceKind k, const SpmvPart& q, const void* alpha, 
   a.ymap = (decltype(a.ymap))(q.ymap);
   a.alpha = *(const T*)alpha;
   a.beta = *(const T*)beta;
-  a.flags = knobs().spmv_flags | (A->csr ? SPMV_PRODA : 0) | (k == kTriple && (A->t_pack & 1) ? SPMV_TPACK : 0);
+  a.flags = knobs().spmv_flags | (A->csr ? SPMV_PRODA : 0) | (k == kTriple && (A->tri.pack & 1) ? SPMV_TPACK : 0);
   a.xcd_chunk = knobs().spmv_xcd_chunk >= 0 ? knobs().spmv_xcd_chunk : A->xcd_auto;
   a.maxlen = d.maxlen;
-  a.soff = (decltype(a.soff))(d.soff);
+  const Sell& S = *d.S;
+  a.soff = (decltype(a.soff))(S.off.p);
   a.slen = (decltype(a.slen))(d.slen);
-  a.col = (decltype(a.col))(d.col);
-  a.col16 = (decltype(a.col16))(d.col16);
-  a.gbase = (decltype(a.gbase))(d.gbase);
-  a.val = (decltype(a.val))((const T*)d.val);
-  a.rowmap = (decltype(a.rowmap))(d.rowmap);
-  a.nrows = d.nrows;
+  a.col = (decltype(a.col))(S.col.p);
+  a.col16 = (decltype(a.col16))(d.codes ? S.col16.p : nullptr);
+  a.gbase = (decltype(a.gbase))(d.codes ? S.gbase.p : nullptr);
+  a.val = (decltype(a.val))((const T*)S.val.p);
+  a.rowmap = (decltype(a.rowmap))(S.rowmap.p);
+  a.nrows = S.nrows;
   if (k == kTriple) {
-    if (knobs().spmv_flags & SPMV_DESC) a.desc = (decltype(a.desc))(A->d_t_desc);
+    if (knobs().spmv_flags & SPMV_DESC) a.desc = (decltype(a.desc))(A->tri.desc.p);
   } else if (k == kPattern) {
-    a.pat = (decltype(a.pat))(A->d_pat);
-    a.mask = (decltype(a.mask))(A->d_mask);
+    a.pat = (decltype(a.pat))(A->d_pat.p);
+    a.mask = (decltype(a.mask))(A->d_mask.p);
     a.kmax = A->kmax;
-    if (knobs().spmv_flags & SPMV_DESC) a.desc = (decltype(a.desc))(A->d_pdesc);
-    if (A->d_uval && a.desc) {
-      a.uval = (decltype(a.uval))((const T*)A->d_uval);
-      a.uK = A->uK;
-      for (int e = 0; e < 8; ++e) a.upat[e] = A->upat[e];
+    if (knobs().spmv_flags & SPMV_DESC) a.desc = (decltype(a.desc))(A->d_pdesc.p);
+    if (A->uni.val && a.desc) {
+      a.uval = (decltype(a.uval))((const T*)A->uni.val.p);
+      a.uK = A->uni.K;
+      for (int e = 0; e < 8; ++e) a.upat[e] = A->uni.pat[e];
     }
   } else if (k == kInt32) {
-    a.sflags = (decltype(a.sflags))(A->d_sflags);
-    a.lmask = (decltype(a.lmask))(A->d_lmask);
+    a.sflags = (decltype(a.sflags))(A->d_sflags.p);
+    a.lmask = (decltype(a.lmask))(A->d_lmask.p);
     // spmv_format 0 runs the delta16 slices (Float32: interleaved rows) as int32
-    if (A->d_col16 && A->R == 4 && !pattern_layout(A)) a.ilv = (decltype(a.ilv))(A->d_kind);
+    if (A->main.col16 && A->R == 4 && !pattern_layout(A)) a.ilv = (decltype(a.ilv))(A->d_kind.p);
   }
   return a;
 }
@@ -2037,7 +2029,7 @@ __global__ void k_spmv_long_fold(int64_t nlong, const int32_t* __restrict__ lrow
 template <typename T, bool ALPHA, int BMODE>
 static void long_t(const pa_mat* A, const void* x, void* y, const int32_t* ymap, const void* alpha, const void* beta,
                    void* dotp, int64_t dot_base, hipStream_t st) {
-  const T* val = (const T*)A->d_val + A->long_off;
+  const T* val = (const T*)A->main.val + A->long_off;
   const T al = *(const T*)alpha, be = *(const T*)beta;
   if (knobs().long_exact) {
     hipLaunchKernelGGL((k_spmv_long_exact<T, ALPHA, BMODE>), dim3((unsigned)A->n_long), dim3(64), 0, st, A->n_long,
@@ -2599,7 +2591,7 @@ __global__ __launch_bounds__(256) void k_pattern_detect(int64_t nrows, int64_t n
   const bool gr = __any(g1);
   const bool ga = __any(ghost_any);
   if (lane == 0) {
-    kind[s] = best ? 1 : 0;
+    kind[s] = best ? kBkPattern : kBkInt32;
     plen[s] = best ? Lp : L;
     pghost[s] = best ? (gr ? 1 : 0) : (ga ? 1 : 0);
     nirreg[s] = best ? nvalid - tot1 : 0;
@@ -2635,7 +2627,7 @@ __global__ __launch_bounds__(256) void k_delta16(int64_t nslices, const int64_t*
   const int64_t s = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (s >= nslices) return;
   const int lane = threadIdx.x & 63;
-  if (kind[s] != 0 || (sflags && sflags[s])) {
+  if (kind[s] != kBkInt32 || (sflags && sflags[s])) {
     if (lane == 0) { ok[s] = 0; gbase[s] = 0; }
     return;
   }
@@ -2698,12 +2690,12 @@ __global__ __launch_bounds__(256) void k_delta16(int64_t nslices, const int64_t*
 }
 
 void launch_delta16(pa_mat* A, int64_t noids, const int32_t* kind, int32_t* ok, hipStream_t st) {
-  const int64_t blocks = (A->nslices + 3) / 4;
+  const int64_t blocks = (A->main.nslices + 3) / 4;
   if (blocks == 0) return;
 #define PA_D16(RR)                                                                                          \
-  hipLaunchKernelGGL(k_delta16<RR>, dim3(blocks), dim3(256), 0, st, A->nslices, A->d_slice_off,              \
-                     A->d_slice_len, A->d_col, kind, A->d_sflags, noids, A->d_col16, A->d_gbase, ok,  \
-                     (unsigned char*)A->d_val)
+  hipLaunchKernelGGL(k_delta16<RR>, dim3(blocks), dim3(256), 0, st, A->main.nslices, A->main.off,              \
+                     A->main.len, A->main.col, kind, A->d_sflags, noids, A->main.col16, A->main.gbase, ok,  \
+                     (unsigned char*)A->main.val)
   switch (A->R) {
     case 1: PA_D16(1); break;
     case 2: PA_D16(2); break;
@@ -2714,11 +2706,11 @@ void launch_delta16(pa_mat* A, int64_t noids, const int32_t* kind, int32_t* ok, 
 
 void launch_pattern_detect(pa_mat* A, int64_t noids, int min_pct, int32_t* kind, int32_t* plen, int32_t* pat,
                            uint64_t* mask, int32_t* pghost, int32_t* nirreg, hipStream_t st) {
-  const int64_t blocks = (A->nslices + 3) / 4;
+  const int64_t blocks = (A->main.nslices + 3) / 4;
   if (blocks == 0) return;
 #define PA_DET(RR)                                                                                      \
-  hipLaunchKernelGGL(k_pattern_detect<RR>, dim3(blocks), dim3(256), 0, st, A->nrows, A->nslices, min_pct, \
-                     A->d_slice_off, A->d_slice_len, A->d_col, noids, A->kmax, kind, plen, pat, mask,  \
+  hipLaunchKernelGGL(k_pattern_detect<RR>, dim3(blocks), dim3(256), 0, st, A->main.nrows, A->main.nslices, min_pct, \
+                     A->main.off, A->main.len, A->main.col, noids, A->kmax, kind, plen, pat, mask,  \
                      pghost, nirreg)
   switch (A->R) {
     case 1: PA_DET(1); break;
@@ -2794,19 +2786,19 @@ void launch_side_len(pa_mat* A, int64_t n, const int32_t* rows, int32_t* len, in
   if (n == 0) return;
   const dim3 g((unsigned)((n + 255) / 256)), b(256);
   switch (A->R) {
-    case 1: hipLaunchKernelGGL(k_side_len<1>, g, b, 0, st, n, rows, A->d_slice_off, A->d_slice_len, A->d_col, len, noids, sghost, A->H); break;
-    case 2: hipLaunchKernelGGL(k_side_len<2>, g, b, 0, st, n, rows, A->d_slice_off, A->d_slice_len, A->d_col, len, noids, sghost, A->H); break;
-    case 4: hipLaunchKernelGGL(k_side_len<4>, g, b, 0, st, n, rows, A->d_slice_off, A->d_slice_len, A->d_col, len, noids, sghost, A->H); break;
+    case 1: hipLaunchKernelGGL(k_side_len<1>, g, b, 0, st, n, rows, A->main.off, A->main.len, A->main.col, len, noids, sghost, A->H); break;
+    case 2: hipLaunchKernelGGL(k_side_len<2>, g, b, 0, st, n, rows, A->main.off, A->main.len, A->main.col, len, noids, sghost, A->H); break;
+    case 4: hipLaunchKernelGGL(k_side_len<4>, g, b, 0, st, n, rows, A->main.off, A->main.len, A->main.col, len, noids, sghost, A->H); break;
   }
 }
 
 template <typename T, int R>
 static void side_fill_t(pa_mat* A, const int32_t* rows, const int32_t* len, hipStream_t st) {
-  const int64_t tot = A->s_nslices * 64 * R;
+  const int64_t tot = A->side.nslices * 64 * R;
   if (tot == 0) return;
   hipLaunchKernelGGL((k_side_fill<T, R>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st,
-                     A->s_nrows, rows, A->d_slice_off, A->d_col, (const T*)A->d_val, A->d_s_off,
-                     A->d_s_len, len, A->d_s_col, (T*)A->d_s_val, A->s_nslices);
+                     A->side.nrows, rows, A->main.off, A->main.col, (const T*)A->main.val, A->side.off,
+                     A->side.len, len, A->side.col, (T*)A->side.val, A->side.nslices);
 }
 
 void launch_side_fill(pa_mat* A, const int32_t* rows, const int32_t* len, hipStream_t st) {
@@ -2899,7 +2891,7 @@ __global__ void k_u_fill(int64_t ns, int H, int K, const int32_t* __restrict__ k
   if (i >= ns * 8 * 64) return;
   const int64_t s = i / (8 * 64);
   const int k = (int)((i / 64) % 8), l = (int)(i % 64);
-  if (kind[s] != 1) return;
+  if (kind[s] != kBkPattern) return;
   const int32_t lraw = plen[s];
   if (k >= (lraw & 0xff)) return;
   const int e = emap[(lraw >> 9) * 8 + k];
@@ -2909,18 +2901,18 @@ __global__ void k_u_fill(int64_t ns, int H, int K, const int32_t* __restrict__ k
 }
 
 void launch_u_fill(const pa_mat* A, hipStream_t st) {
-  const int64_t n = A->nslices * 8 * 64;
-  if (n == 0 || !A->d_uval) return;
-  hipLaunchKernelGGL((k_u_fill<double, 2>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, A->nslices, A->H,
-                     A->uK, A->d_kind, A->d_slice_off, A->d_plen, A->d_uemap, (const double*)A->d_val,
-                     (double*)A->d_uval);
+  const int64_t n = A->main.nslices * 8 * 64;
+  if (n == 0 || !A->uni.val) return;
+  hipLaunchKernelGGL((k_u_fill<double, 2>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, A->main.nslices, A->H,
+                     A->uni.K, A->d_kind, A->main.off, A->d_plen, A->uni.emap, (const double*)A->main.val,
+                     (double*)A->uni.val);
 }
 
 void launch_t_pairinfo(const pa_mat* A, int64_t n, const int32_t* rows, int32_t* pairable, hipStream_t st) {
   if (n == 0) return;
   const dim3 g((unsigned)((n + 255) / 256)), b(256);
-#define PA_TPI(RR) hipLaunchKernelGGL(k_t_pairinfo<RR>, g, b, 0, st, n, rows, A->H, A->d_slice_off, A->d_slice_len, \
-                                      A->d_col, pairable)
+#define PA_TPI(RR) hipLaunchKernelGGL(k_t_pairinfo<RR>, g, b, 0, st, n, rows, A->H, A->main.off, A->main.len, \
+                                      A->main.col, pairable)
   switch (A->R) {
     case 1: PA_TPI(1); break;
     case 2: PA_TPI(2); break;
@@ -3045,18 +3037,18 @@ __global__ void k_t_check(int64_t npos, int64_t nrows, int H, int R, const int32
 }
 
 void launch_t_check(const pa_mat* A, unsigned* bad, hipStream_t st) {
-  const int64_t npos = A->t_nslices * A->H;
+  const int64_t npos = A->tri.nslices * A->H;
   if (npos == 0) return;
-  hipLaunchKernelGGL(k_t_check, dim3((unsigned)((npos + 255) / 256)), dim3(256), 0, st, npos, A->t_nrows, A->H, A->R,
-                     A->d_t_rowmap, A->d_t_off, A->d_t_len, A->d_t_gbase, A->d_t_col16, A->ncols_lids, A->t_pack,
+  hipLaunchKernelGGL(k_t_check, dim3((unsigned)((npos + 255) / 256)), dim3(256), 0, st, npos, A->tri.nrows, A->H, A->R,
+                     A->tri.rowmap, A->tri.off, A->tri.len, A->tri.gbase, A->tri.col16, A->ncols_lids, A->tri.pack,
                      dtype_size(A->dtype) == 4 ? 9 : 4, bad);
 }
 
 void launch_t_rowinfo(const pa_mat* A, int64_t n, const int32_t* rows, int64_t noids, int32_t* info, hipStream_t st) {
   if (n == 0) return;
   const dim3 g((unsigned)((n + 255) / 256)), b(256);
-#define PA_TRI(RR) hipLaunchKernelGGL(k_t_rowinfo<RR>, g, b, 0, st, n, rows, A->H, A->d_slice_off, A->d_slice_len, \
-                                      A->d_col, noids, info)
+#define PA_TRI(RR) hipLaunchKernelGGL(k_t_rowinfo<RR>, g, b, 0, st, n, rows, A->H, A->main.off, A->main.len, \
+                                      A->main.col, noids, info)
   switch (A->R) {
     case 1: PA_TRI(1); break;
     case 2: PA_TRI(2); break;
@@ -3066,10 +3058,10 @@ void launch_t_rowinfo(const pa_mat* A, int64_t n, const int32_t* rows, int64_t n
 }
 
 void launch_t_gbase(const pa_mat* A, int64_t noids, int32_t* ok, hipStream_t st) {
-  const int64_t blocks = (A->t_nslices + 3) / 4;
+  const int64_t blocks = (A->tri.nslices + 3) / 4;
   if (blocks == 0) return;
-#define PA_TGB(RR) hipLaunchKernelGGL(k_t_gbase<RR>, dim3((unsigned)blocks), dim3(256), 0, st, A->t_nslices, \
-                                      A->t_nrows, A->H, A->d_t_rowlen, A->d_t_src, A->d_col, noids, A->d_t_gbase, ok)
+#define PA_TGB(RR) hipLaunchKernelGGL(k_t_gbase<RR>, dim3((unsigned)blocks), dim3(256), 0, st, A->tri.nslices, \
+                                      A->tri.nrows, A->H, A->tri.rowlen, A->tri.src, A->main.col, noids, A->tri.gbase, ok)
   switch (A->R) {
     case 1: PA_TGB(1); break;
     case 2: PA_TGB(2); break;
@@ -3080,12 +3072,12 @@ void launch_t_gbase(const pa_mat* A, int64_t noids, int32_t* ok, hipStream_t st)
 
 // codes false: values only (pa_mat_set_values, fillstored, exchange!(A))
 void launch_t_fill(const pa_mat* A, int64_t noids, bool codes, hipStream_t st) {
-  if (A->t_nrows == 0) return;
-  const dim3 g((unsigned)((A->t_nrows + 255) / 256)), b(256);
+  if (A->tri.nrows == 0) return;
+  const dim3 g((unsigned)((A->tri.nrows + 255) / 256)), b(256);
 #define PA_TF(E, RR)                                                                                           \
-  hipLaunchKernelGGL((k_t_fill<E, RR>), g, b, 0, st, A->t_nrows, A->H, A->d_t_rowmap, A->d_t_rowlen, A->d_t_src, \
-                     A->d_t_off, A->d_t_len, A->d_t_gbase, A->d_col, (const E*)A->d_val, noids, codes,          \
-                     A->t_pack, A->d_t_col16, (E*)A->d_t_val)
+  hipLaunchKernelGGL((k_t_fill<E, RR>), g, b, 0, st, A->tri.nrows, A->H, A->tri.rowmap, A->tri.rowlen, A->tri.src, \
+                     A->tri.off, A->tri.len, A->tri.gbase, A->main.col, (const E*)A->main.val, noids, codes,          \
+                     A->tri.pack, A->tri.col16, (E*)A->tri.val)
   switch (A->dtype) {
     case PA_F32:
       if (A->R == 2) PA_TF(float, 2);

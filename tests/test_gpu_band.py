@@ -26,9 +26,10 @@ import contextlib
 import numpy as np
 import pytest
 
+from matrix_cases import SEED, rand as _rand, unsorted_csr as _unsorted_csr
+
 gpu = pytest.mark.gpu
 
-SEED = 20250114
 DTYPES = [np.float64, np.float32, np.complex128, np.complex64]
 AB = [(1.0, 0.0), (-1.3, 0.5)]
 
@@ -71,13 +72,6 @@ def _knobs(pamd, **kw):
     finally:
         for k, v in reversed(prev):
             pamd._lib.tune(k, v)
-
-
-def _rand(rng, n, dtype):
-    dtype = np.dtype(dtype)
-    if dtype.kind == "c":
-        return (rng.uniform(-1, 1, n) + 1j * rng.uniform(-1, 1, n)).astype(dtype)
-    return rng.uniform(-1, 1, n).astype(dtype)
 
 
 def _real(dtype):
@@ -428,23 +422,6 @@ def test_band_device_cg(be, pamd, O, n, nparts, dtype, fuse):
             np.testing.assert_allclose(hs[1][:k], oh[:k], rtol=5e-6)
         else:
             np.testing.assert_allclose(hs[1], oh, rtol=1e-8, atol=1e-14)
-
-
-def _unsorted_csr(n, D, Bi, order, dtype):
-    """rowptr, colval (Bi-based), nzval of the band matrix with every row
-    stored diagonal first and the others ascending, or descending; the
-    triplets in that order too."""
-    rows, cols = [], []
-    for i in range(n):
-        js = [i + d for d in sorted(D) if 0 <= i + d < n]
-        js = ([i] + [j for j in js if j != i]) if order == "diag_first" else js[::-1]
-        rows += [i] * len(js)
-        cols += js
-    I, J = np.asarray(rows, np.int64), np.asarray(cols, np.int64)
-    rowptr = np.concatenate([[0], np.cumsum(np.bincount(I, minlength=n))]).astype(np.int64) + Bi
-    rng = np.random.default_rng([SEED, 13, n, len(D)])
-    V = _rand(rng, len(I), dtype)
-    return rowptr, J + Bi, V, I + 1, J + 1, _rand(rng, n, dtype)
 
 
 @gpu

@@ -7,6 +7,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from matrix_cases import long_row_coo as _long_row_coo
+
 pytestmark = pytest.mark.gpu
 
 
@@ -221,27 +223,6 @@ def test_device_to_lids_unknown_gid(be, pamd):
     with pytest.raises(pamd.PAError, match="KeyError"):
         pamd.DeviceMatrix.from_coo(ctx, I, I, np.ones(3), pamd.device.device_index_gids(ctx, s),
                                    pamd.device.device_index_gids(ctx, s), 10, 10, ids_global=True)
-
-
-def _long_row_coo(rng, part, p, dtype, long_lens):
-    """owned rows with ~9 entries, a few rows with long_lens entries (over all
-    local columns, ghosts included), in random order with duplicates."""
-    s = part.partition.local(p)
-    own = s.oid_to_lid
-    I, J = [], []
-    longs = rng.choice(own, size=min(len(long_lens), len(own)), replace=False)
-    for li in own:
-        k = 9
-        if li in longs:
-            k = long_lens[list(longs).index(li)]
-        I += [li] * k
-        J += list(rng.integers(1, s.num_lids + 1, size=k))
-    I, J = np.array(I), np.array(J)
-    o = rng.permutation(len(I))
-    V = rng.uniform(-1, 1, len(I))
-    if np.dtype(dtype).kind == "c":
-        V = V + 1j * rng.uniform(-1, 1, len(I))
-    return I[o], J[o], V[o].astype(dtype), sorted(int(v) for v in longs)
 
 
 def _ref_spmv(H, s, xl, yl, alpha, beta, dtype):

@@ -4,6 +4,8 @@ parts without neighbours, an empty COO, and the CG on such partitions."""
 import numpy as np
 import pytest
 
+from matrix_cases import tridiag as _tridiag
+
 pytestmark = pytest.mark.gpu
 
 
@@ -12,18 +14,6 @@ def be(pamd):
     if pamd.device_count() == 0:
         pytest.fail("no HIP device visible: the GPU tests need the MI355X")
     return pamd.HIPBackend(devices=[0])
-
-
-def _tridiag(n, part_rows):
-    """global-id COO of the owned rows of a 1-D Laplacian-like matrix."""
-    I, J, V = [], [], []
-    for g in part_rows:
-        for d, v in ((-1, -1.0), (0, 4.0), (1, -1.5)):
-            if 1 <= g + d <= n:
-                I.append(g)
-                J.append(g + d)
-                V.append(v + 0.01 * g)
-    return np.array(I, np.int64), np.array(J, np.int64), np.array(V)
 
 
 def _build(pamd, O, parts, n, nparts):

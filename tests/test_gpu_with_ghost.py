@@ -8,6 +8,8 @@ the oracle."""
 import numpy as np
 import pytest
 
+from matrix_cases import with_ghost_coo as _coo
+
 pytestmark = pytest.mark.gpu
 
 SEED = 20250114
@@ -18,29 +20,6 @@ def be(pamd):
     if pamd.device_count() == 0:
         pytest.fail("no HIP device visible: the GPU tests need the MI355X")
     return pamd.HIPBackend(devices=[0])
-
-
-def _coo(rows, parts, ngids, periodic, rng):
-    D = len(ngids)
-    per = periodic or (False,) * D
-    I, J, V = {}, {}, {}
-    for p in parts.part_ids:
-        s = rows.partition.local(p)
-        own = s.lid_to_gid[s.oid_to_lid - 1]
-        ci = [(own - 1) // int(np.prod(ngids[:d])) % ngids[d] for d in range(D)]
-        ii, jj = [own], [own]
-        for d in range(D):
-            for step in (-1, 1):
-                c = ci[d] + step
-                ok = np.ones(len(own), bool) if per[d] else (c >= 0) & (c < ngids[d])
-                c = c % ngids[d]
-                nb = own + (c - ci[d]) * int(np.prod(ngids[:d]))
-                ii.append(own[ok])
-                jj.append(nb[ok])
-        I[p] = np.concatenate(ii)
-        J[p] = np.concatenate(jj)
-        V[p] = rng.uniform(-1, 1, len(I[p]))
-    return I, J, V
 
 
 @pytest.mark.parametrize("shape,ngids,periodic", [((2, 2, 2), (12, 10, 9), None), ((2, 2, 1), (16, 14, 6), (True, False, True)),
