@@ -2607,9 +2607,10 @@ __global__ __launch_bounds__(256) void k_pattern_detect(int64_t nrows, int64_t n
 }
 
 // delta16 eligibility and codes, one wave per slice: an int32-column slice
-// (kind 0, no long rows) becomes delta16 when every owned column is within
-// ±16383 of its row and every ghost column within 32766 of the slice's
-// smallest ghost column.  Float32 slices' rows are then re-laid out
+// (kind 0, no long rows) becomes delta16 when every owned column is its row
+// plus a signed 15-bit delta, [-16384, 16383], and every ghost column within
+// 32766 of the slice's smallest (32767 would be 0xFFFF, the padding code).
+// Float32 slices' rows are then re-laid out
 // interleaved (row w of the slice at lane w % 64, position w / 64, instead
 // of lane w / R, position w % R), values and int32 ids moved in place,
 // block k by block k; the codes go to col16 in the (new) slots: a gather

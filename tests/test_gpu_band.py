@@ -21,12 +21,11 @@ row when b is odd, the high end when n-1-b is even.
 Every test but the last needs the GPU and carries the gpu mark itself (the
 module has no pytestmark: the long-double reference is checked against the
 oracle on the CPU)."""
-import contextlib
-
 import numpy as np
 import pytest
 
-from matrix_cases import SEED, rand as _rand, unsorted_csr as _unsorted_csr
+from matrix_cases import (SEED, _as_array, _eq, _knobs, _nan, _real, _sel, _to_oracle, check_bound, rand as _rand,
+                          unsorted_csr as _unsorted_csr)
 
 gpu = pytest.mark.gpu
 
@@ -61,47 +60,6 @@ def be(pamd):
     return pamd.HIPBackend(devices=[0])
 
 
-@contextlib.contextmanager
-def _knobs(pamd, **kw):
-    """pa_tune knobs for the body, every one restored afterwards."""
-    prev = []
-    try:
-        for k, v in kw.items():
-            prev.append((k, pamd._lib.tune(k, v)))
-        yield
-    finally:
-        for k, v in reversed(prev):
-            pamd._lib.tune(k, v)
-
-
-def _real(dtype):
-    return np.float32 if np.dtype(dtype) in (np.dtype(np.float32), np.dtype(np.complex64)) else np.float64
-
-
-def _nan(n, dtype):
-    v = np.empty(n, dtype)
-    v[:] = np.nan + (1j * np.nan if np.dtype(dtype).kind == "c" else 0)
-    return v
-
-
-def _to_oracle(O, a):
-    return O.Cx(a.real.copy(), a.imag.copy()) if np.iscomplexobj(a) else a.copy()
-
-
-def _eq(O, got, ref):
-    if isinstance(ref, O.Cx):
-        return np.array_equal(got.real, ref.re) and np.array_equal(got.imag, ref.im)
-    return np.array_equal(got, ref)
-
-
-def _sel(O, ref, idx):
-    return O.Cx(ref.re[idx], ref.im[idx]) if isinstance(ref, O.Cx) else ref[idx]
-
-
-def _as_array(O, ref):
-    return ref.re + 1j * ref.im if isinstance(ref, O.Cx) else ref
-
-
 def band_coo(n, D, dtype, seed, spd=False):
     """The band matrix's global COO in row order (1-based gids) and a global
     x.  spd: diagonal 4 + 0.01*i, off-diagonals -1 (D3 only)."""
@@ -117,35 +75,6 @@ def band_coo(n, D, dtype, seed, spd=False):
         V = np.where(I == J, 4.0 + 0.01 * I, -1.0).astype(dtype)
     x = _rand(rng, n, dtype)
     return I, J, V, x
-
-
-def ref_longdouble(n, I, J, V, x):
-    """y = A*x straight from the triplets in extended precision (no code of
-    the oracle's): the sums, Σ|v||x| and the entry count of every row."""
-    wide = np.clongdouble if np.iscomplexobj(V) else np.longdouble
-    v, xj = V.astype(wide), x.astype(wide)[J - 1]
-    y = np.zeros(n, wide)
-    np.add.at(y, I - 1, v * xj)
-    mag = np.zeros(n, np.longdouble)
-    np.add.at(mag, I - 1, np.abs(v).astype(np.longdouble) * np.abs(xj).astype(np.longdouble))
-    return y, mag, np.bincount(I - 1, minlength=n)
-
-
-def check_bound(y, n, I, J, V, x, what):
-    """|y[i] - y_ref[i]| <= k_i * eps * Σ|v||x|: recursive summation of a row
-    of k terms has relative error γ_k ~ k*u of Σ|v||x| with unit roundoff
-    u = eps/2 (one more for the product), so k_i = entries + 1 leaves a factor
-    2; a complex product carries about 2.8 unit roundoffs: entries + 4."""
-    yref, mag, cnt = ref_longdouble(n, I, J, V, x)
-    eps = np.finfo(_real(V.dtype)).eps
-    k = cnt + (4 if np.iscomplexobj(V) else 1)
-    err = np.abs(y.astype(yref.dtype) - yref).astype(np.longdouble)
-    bound = k * np.longdouble(eps) * mag
-    worst = float(np.max(err / np.maximum(bound, np.finfo(np.longdouble).tiny)))
-    print(f"{what}: largest error / bound = {worst:.3g}")
-    bad = np.flatnonzero(~(err <= bound))  # a NaN fails
-    assert bad.size == 0, f"{what}: {bad.size} rows miss the long-double bound, first gid {bad[0] + 1}: " \
-                          f"error {float(err[bad[0]]):.3e}, bound {float(bound[bad[0]]):.3e}"
 
 
 def oracle_band(O, nparts, n, I, J, V):
