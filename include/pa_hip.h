@@ -452,6 +452,21 @@ int pa_coo_download(const pa_coo* coo, int64_t* I, int64_t* J, void* V);
  * a KeyError (to_lids!, Interfaces.jl:2420).                              */
 int pa_coo_assemble_all(int n, pa_coo* const coo[], const pa_index* const rows[],
                         pa_xchg* const rows_xchg[]);
+/* async_exchange!(I, J, V, rows) + wait (Interfaces.jl:2494-2592) over the
+ * n parts of this process, the mirror of pa_coo_assemble_all: each triplet
+ * whose row (a gid of rows, which needs pa_index_set_gids) another part
+ * holds as a ghost is copied to that part — segments in
+ * rows.exchanger.parts_snd order, input order inside — and stays in the
+ * local list unchanged.  A row that several neighbours hold goes to the
+ * last of them in parts_snd order only (`lid_to_i[lid] = i` overwrites,
+ * 2514-2520).  A triplet of a ghost row that is sent nowhere keeps its place
+ * and its value becomes zero(Tv), an exact +0 (2529-2530).  Every part
+ * appends what it receives in parts_rcv order.  I and J stay global.
+ * Transport, preconditions and the KeyError of an unknown row gid as in
+ * pa_coo_assemble_all; a neighbour that does not list the partner back is
+ * an "exchanger mismatch" error.                                          */
+int pa_coo_exchange_all(int n, pa_coo* const coo[], const pa_index* const rows[],
+                        pa_xchg* const rows_xchg[]);
 /* pa_mat_from_coo over a device COO (index_bytes 8): ids_global = 1 maps
  * I, J through rows' and cols' gid tables; the COO is left unchanged.    */
 int pa_mat_from_dcoo(const pa_coo* coo, int ids_global, int64_t nrows_lids,

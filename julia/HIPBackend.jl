@@ -19,7 +19,8 @@
 #     comparisons as one pa_vec_eval pass), ==, maximum / minimum, sum of a
 #     broadcast, the Euclidean distances (1682-1686, 1774-1863),
 #     IterativeSolvers.cg! (v0.9, test_fdm.jl:115), and the COO triplet
-#     exchange assemble!(I, J, V, rows) (2406-2492);
+#     exchanges assemble!(I, J, V, rows) (2406-2492) and
+#     exchange!(I, J, V, rows) (2494-2592);
 #   * everything else (PRange, Exchanger, add_gids!, gather/scatter setup
 #     collectives) runs unchanged on the host parts.
 #
@@ -531,10 +532,8 @@ function _idx_gids_handle(ctx::PartCtx, ids)
   end
   h
 end
-function async_assemble!(I::HIPData{<:Vector{<:Integer}}, J::HIPData{<:Vector{<:Integer}},
-                         V::HIPData{<:Vector{T}}, rows::PRange,
-                         t0::AbstractPData=PartitionedArrays._empty_tasks(rows.exchanger.parts_rcv)) where {T<:DeviceEltype}
-  _wait_all(t0)
+# to_ghosts = false: pa_coo_assemble_all; true: pa_coo_exchange_all
+function _coo_all!(to_ghosts::Bool, I::HIPData, J::HIPData, V::HIPData{<:Vector{T}}, rows::PRange) where {T}
   n = length(I.parts)
   coo = Vector{Ptr{Cvoid}}(undef, n)
   for i in 1:n
@@ -547,8 +546,13 @@ function async_assemble!(I::HIPData{<:Vector{<:Integer}}, J::HIPData{<:Vector{<:
   end
   try
     ri = [_idx_gids_handle(rows.partition.ctxs[i], rows.partition.parts[i]) for i in 1:n]
-    check(ccall((:pa_coo_assemble_all, libpa), Cint,
-                (Cint, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}), n, coo, ri, dev_xchg(rows)))
+    if to_ghosts
+      check(ccall((:pa_coo_exchange_all, libpa), Cint,
+                  (Cint, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}), n, coo, ri, dev_xchg(rows)))
+    else
+      check(ccall((:pa_coo_assemble_all, libpa), Cint,
+                  (Cint, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}), n, coo, ri, dev_xchg(rows)))
+    end
     for i in 1:n
       m = Ref{Int64}(0)
       check(ccall((:pa_coo_size, libpa), Cint, (Ptr{Cvoid}, Ref{Int64}), coo[i], m))
@@ -563,6 +567,26 @@ function async_assemble!(I::HIPData{<:Vector{<:Integer}}, J::HIPData{<:Vector{<:
     foreach(h -> ccall((:pa_coo_destroy, libpa), Cint, (Ptr{Cvoid},), h), coo)
   end
   _done_tasks(I)
+end
+function async_assemble!(I::HIPData{<:Vector{<:Integer}}, J::HIPData{<:Vector{<:Integer}},
+                         V::HIPData{<:Vector{T}}, rows::PRange,
+                         t0::AbstractPData=PartitionedArrays._empty_tasks(rows.exchanger.parts_rcv)) where {T<:DeviceEltype}
+  _wait_all(t0)
+  _coo_all!(false, I, J, V, rows)
+end
+
+# ---- exchange!(I, J, V, rows) (Interfaces.jl:2494-2592) --------------------
+# the mirror of the assembly: the owners' triplets of the rows that other
+# parts hold as ghosts are copied to those parts on the device
+# (pa_coo_exchange_all; a row held by several neighbours goes to the last of
+# them in parts_snd order, as the reference's lid_to_i does), unsent ghost
+# rows' values become zero(T); exchange! itself is the reference's generic
+# schedule-and-wait over the tasks returned here (453-458)
+function async_exchange!(I::HIPData{<:Vector{<:Integer}}, J::HIPData{<:Vector{<:Integer}},
+                         V::HIPData{<:Vector{T}}, rows::PRange,
+                         t0::AbstractPData=PartitionedArrays._empty_tasks(rows.exchanger.parts_rcv)) where {T<:DeviceEltype}
+  _wait_all(t0)
+  _coo_all!(true, I, J, V, rows)
 end
 
 # ---- reductions (Interfaces.jl:221-238, 1767-1772, 1973-1992) -------------

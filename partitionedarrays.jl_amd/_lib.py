@@ -96,6 +96,7 @@ _SIGS = {
     "pa_coo_size": [_p, _i64p],
     "pa_coo_download": [_p, _i64p, _i64p, _p],
     "pa_coo_assemble_all": [C.c_int, C.POINTER(_p), C.POINTER(_p), C.POINTER(_p)],
+    "pa_coo_exchange_all": [C.c_int, C.POINTER(_p), C.POINTER(_p), C.POINTER(_p)],
     "pa_mat_from_dcoo": [_p, C.c_int, C.c_int64, C.c_int64, _p, _p, _i64p, _i64p, _i64p, C.POINTER(_p)],
     "pa_mat_from_coo": [_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, _p, _p, _p, _p, _p, _i64p,
                         _i64p, _i64p, C.POINTER(_p)],

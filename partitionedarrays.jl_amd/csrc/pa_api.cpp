@@ -113,6 +113,10 @@ int coo_assemble_pack(int dtype, int64_t n, const int64_t* I, const int64_t* J, 
                       const int64_t* slid, int64_t nl, const std::vector<int32_t>& lid_to_ohid, int nseg,
                       const int32_t* d_lids_rcv, const std::vector<int64_t>& ptrs_rcv, int64_t** sI, int64_t** sJ,
                       void** sV, std::vector<int64_t>* cnt, hipStream_t st);
+int coo_exchange_pack(int dtype, int64_t n, const int64_t* I, const int64_t* J, void* V, const uint64_t* sgid,
+                      const int64_t* slid, int64_t nl, const std::vector<int32_t>& lid_to_ohid, int nseg,
+                      const int32_t* d_lids_snd, const std::vector<int64_t>& ptrs_snd, int64_t** sI, int64_t** sJ,
+                      void** sV, std::vector<int64_t>* cnt, hipStream_t st);
 int gids_first_touch(int64_t n, const int64_t* gids, const uint64_t* sgid, const int64_t* slid, int64_t nl,
                      int64_t** out, int64_t* m_out, hipStream_t st);
 // ev (optional): recorded on st when the kernel completes (one runtime call)
@@ -2728,6 +2732,264 @@ int mat_from_coo_impl(pa_ctx* c, int dtype, int index_bytes, int ids_global, int
   if (rc == 0 && !again) tr.mark("pattern slices");
   return rc;
 }
+
+// ---------------------------------------------------------------------------
+// The transport shared by assemble!(I, J, V, rows) and exchange!(I, J, V,
+// rows).  One part's side: the triplets it sends (segment after segment, in
+// the order of its sending neighbour list), their counts and offsets; the
+// counts it receives (in the order of its receiving neighbour list); the new
+// lists.
+struct CooSide {
+  int64_t *sI = nullptr, *sJ = nullptr;
+  void* sV = nullptr;
+  std::vector<int64_t> cnt, off, rcnt, roff;
+  int64_t *nI = nullptr, *nJ = nullptr;
+  void* nV = nullptr;
+  int64_t nn = 0;
+};
+
+void coo_free_sides(int n, pa_coo* const coo[], std::vector<CooSide>& sd) {
+  for (int i = 0; i < n; ++i) {
+    (void)hipSetDevice(coo[i]->ctx->device);
+    for (void* p : {(void*)sd[i].sI, (void*)sd[i].sJ, sd[i].sV, (void*)sd[i].nI, (void*)sd[i].nJ, sd[i].nV})
+      if (p) (void)hipFree(p);
+    sd[i] = CooSide{};
+  }
+}
+
+// sd[i].sI/sJ/sV/cnt hold part i's packed segments.  to_ghosts = false
+// (assemble!): a part sends to its parts_rcv and receives from its
+// parts_snd; to_ghosts = true (exchange!): it sends to its parts_snd and
+// receives from its parts_rcv.  Delivery is the reference's
+// (SequentialBackend.jl:167-200 / MPIBackend.jl:261-309): the sender's
+// segment for q lands in q's slot of the sender.  Counts go first, then I,
+// J, V per segment: device / peer copies between the parts of this process,
+// one RCCL group for the others.  Every part ends with its own triplets
+// followed by the received segments in the order of its receiving list; sd
+// is freed on return.
+int coo_move_segments(const char* who, int n, pa_coo* const coo[], pa_xchg* const xg[], std::vector<CooSide>& sd,
+                      bool to_ghosts) {
+  const size_t S = dtype_size(coo[0]->dtype);
+  auto to_list = [&](const pa_xchg* X) -> const std::vector<int32_t>& { return to_ghosts ? X->parts_snd : X->parts_rcv; };
+  auto from_list = [&](const pa_xchg* X) -> const std::vector<int32_t>& { return to_ghosts ? X->parts_rcv : X->parts_snd; };
+  const char* to_name = to_ghosts ? "parts_snd" : "parts_rcv";
+  const char* from_name = to_ghosts ? "parts_rcv" : "parts_snd";
+  auto free_all = [&]() { coo_free_sides(n, coo, sd); };
+  for (int i = 0; i < n; ++i) {
+    sd[i].off.assign(sd[i].cnt.size() + 1, 0);
+    for (size_t k = 0; k < sd[i].cnt.size(); ++k) sd[i].off[k + 1] = sd[i].off[k] + sd[i].cnt[k];
+  }
+  // 2. the counts each part receives, per entry of its receiving list
+  LocalSet L = local_set(n, xg);
+  bool remote = false;
+  for (int i = 0; i < n; ++i) {
+    pa_xchg* X = xg[i];
+    const auto& from = from_list(X);
+    sd[i].rcnt.assign(from.size(), 0);
+    for (size_t j = 0; j < from.size(); ++j) {
+      const int jj = L.find(from[j]);
+      if (jj < 0) { remote = true; continue; }
+      const auto& q = to_list(xg[jj]);
+      const auto it = std::find(q.begin(), q.end(), X->ctx->part);
+      if (it == q.end()) {
+        free_all();
+        PA_FAIL(std::string(who) + ": exchanger mismatch (a part in " + from_name + " does not list this part in " +
+                to_name + ")");
+      }
+      sd[i].rcnt[j] = sd[jj].cnt[it - q.begin()];
+    }
+    for (int32_t q : to_list(X)) {
+      const int jj = L.find(q);
+      if (jj < 0) { remote = true; continue; }
+      const auto& back = from_list(xg[jj]);  // a segment nobody receives would be lost silently
+      if (std::find(back.begin(), back.end(), X->ctx->part) == back.end()) {
+        free_all();
+        PA_FAIL(std::string(who) + ": exchanger mismatch (a part in " + to_name + " does not list this part in " +
+                from_name + ")");
+      }
+    }
+  }
+  if (remote) {  // counts of the other processes' parts: one RCCL group of 8 B messages
+    std::vector<int64_t*> dsc(n, nullptr), drc(n, nullptr);
+    auto free_cnt = [&]() {
+      for (int i = 0; i < n; ++i) { (void)hipSetDevice(coo[i]->ctx->device); dev_free(dsc[i]); dev_free(drc[i]); }
+    };
+    std::vector<P2P> ops;
+    for (int i = 0; i < n; ++i) {
+      pa_xchg* X = xg[i];
+      pa_ctx* c = X->ctx;
+      const auto &to = to_list(X), &from = from_list(X);
+      if (!c->comm) {
+        free_cnt();
+        free_all();
+        PA_FAIL(std::string(who) + ": a neighbour is not held by this process and no RCCL communicator was initialised");
+      }
+      HIPC(hipSetDevice(c->device));
+      if (dev_upload(&dsc[i], sd[i].cnt)) { free_cnt(); free_all(); return -1; }
+      if (!from.empty()) HIPC(hipMalloc((void**)&drc[i], from.size() * 8));
+      for (size_t k = 0; k < to.size(); ++k)
+        if (L.find(to[k]) < 0)
+          ops.push_back({c->part, to[k], true, (char*)(dsc[i] + k), 8, c->peer_rank(to[k]), (ncclComm_t)c->comm,
+                         c->s_main});
+      for (size_t j = 0; j < from.size(); ++j)
+        if (L.find(from[j]) < 0)
+          ops.push_back({from[j], c->part, false, (char*)(drc[i] + j), 8, c->peer_rank(from[j]), (ncclComm_t)c->comm,
+                         c->s_main});
+    }
+    if (rccl_group(ops)) { free_cnt(); free_all(); return -1; }
+    for (int i = 0; i < n; ++i) {
+      pa_xchg* X = xg[i];
+      const auto& from = from_list(X);
+      HIPC(hipSetDevice(X->ctx->device));
+      HIPC(hipStreamSynchronize(X->ctx->s_main));
+      std::vector<int64_t> got(from.size());
+      if (!got.empty()) HIPC(hipMemcpy(got.data(), drc[i], got.size() * 8, hipMemcpyDeviceToHost));
+      for (size_t j = 0; j < from.size(); ++j)
+        if (L.find(from[j]) < 0) sd[i].rcnt[j] = got[j];
+    }
+    free_cnt();
+  }
+  // 3. the new lists: the local triplets, then the received segments in the
+  // order of the receiving list (Interfaces.jl:2470-2486, 2570-2586)
+  for (int i = 0; i < n; ++i) {
+    pa_coo* C = coo[i];
+    CooSide& d = sd[i];
+    d.roff.assign(d.rcnt.size() + 1, 0);
+    for (size_t j = 0; j < d.rcnt.size(); ++j) d.roff[j + 1] = d.roff[j] + d.rcnt[j];
+    d.nn = C->n + d.roff.back();
+    HIPC(hipSetDevice(C->ctx->device));
+    if (d.nn > 0) {
+      hipError_t e = hipMalloc((void**)&d.nI, d.nn * 8);
+      if (e == hipSuccess) e = hipMalloc((void**)&d.nJ, d.nn * 8);
+      if (e == hipSuccess) e = hipMalloc(&d.nV, d.nn * S);
+      if (e != hipSuccess) { free_all(); HIPC(e); }
+    }
+    if (C->n > 0) {
+      hipStream_t st = C->ctx->s_main;
+      HIPC(hipMemcpyAsync(d.nI, C->d_I, C->n * 8, hipMemcpyDeviceToDevice, st));
+      HIPC(hipMemcpyAsync(d.nJ, C->d_J, C->n * 8, hipMemcpyDeviceToDevice, st));
+      HIPC(hipMemcpyAsync(d.nV, C->d_V, C->n * S, hipMemcpyDeviceToDevice, st));
+    }
+  }
+  for (int i = 0; i < n; ++i) {  // every pack has finished before any part reads it
+    HIPC(hipSetDevice(coo[i]->ctx->device));
+    HIPC(hipStreamSynchronize(coo[i]->ctx->s_main));
+  }
+  // 4. the segments: device copies between the parts of this process, one
+  // RCCL group (I, J, V per segment) for the others
+  std::vector<P2P> ops;
+  for (int i = 0; i < n; ++i) {
+    pa_xchg* X = xg[i];
+    pa_ctx* c = X->ctx;
+    CooSide& d = sd[i];
+    const auto &to = to_list(X), &from = from_list(X);
+    HIPC(hipSetDevice(c->device));
+    for (size_t j = 0; j < from.size(); ++j) {
+      const int64_t m = d.rcnt[j];
+      if (m == 0) continue;
+      const int64_t at = coo[i]->n + d.roff[j];
+      const int jj = L.find(from[j]);
+      if (jj < 0) {
+        const int q = from[j], pr = c->peer_rank(q);
+        ncclComm_t cm = (ncclComm_t)c->comm;
+        ops.push_back({q, c->part, false, (char*)(d.nI + at), (size_t)m * 8, pr, cm, c->s_main});
+        ops.push_back({q, c->part, false, (char*)(d.nJ + at), (size_t)m * 8, pr, cm, c->s_main});
+        ops.push_back({q, c->part, false, (char*)d.nV + at * S, (size_t)m * S, pr, cm, c->s_main});
+        continue;
+      }
+      const auto& qt = to_list(xg[jj]);
+      const int64_t k = std::find(qt.begin(), qt.end(), c->part) - qt.begin();
+      const CooSide& src = sd[jj];
+      const int64_t from_at = src.off[k];
+      const int sdev = xg[jj]->ctx->device;
+      if (sdev == c->device) {
+        HIPC(hipMemcpyAsync(d.nI + at, src.sI + from_at, m * 8, hipMemcpyDeviceToDevice, c->s_main));
+        HIPC(hipMemcpyAsync(d.nJ + at, src.sJ + from_at, m * 8, hipMemcpyDeviceToDevice, c->s_main));
+        HIPC(hipMemcpyAsync((char*)d.nV + at * S, (const char*)src.sV + from_at * S, m * S, hipMemcpyDeviceToDevice,
+                            c->s_main));
+      } else {
+        HIPC(hipMemcpyPeerAsync(d.nI + at, c->device, src.sI + from_at, sdev, m * 8, c->s_main));
+        HIPC(hipMemcpyPeerAsync(d.nJ + at, c->device, src.sJ + from_at, sdev, m * 8, c->s_main));
+        HIPC(hipMemcpyPeerAsync((char*)d.nV + at * S, c->device, (const char*)src.sV + from_at * S, sdev, m * S,
+                                c->s_main));
+      }
+    }
+    for (size_t k = 0; k < to.size(); ++k) {
+      const int64_t m = d.cnt[k];
+      const int q = to[k];
+      if (m == 0 || L.find(q) >= 0) continue;
+      const int pr = c->peer_rank(q);
+      ncclComm_t cm = (ncclComm_t)c->comm;
+      ops.push_back({c->part, q, true, (char*)(d.sI + d.off[k]), (size_t)m * 8, pr, cm, c->s_main});
+      ops.push_back({c->part, q, true, (char*)(d.sJ + d.off[k]), (size_t)m * 8, pr, cm, c->s_main});
+      ops.push_back({c->part, q, true, (char*)d.sV + d.off[k] * S, (size_t)m * S, pr, cm, c->s_main});
+    }
+  }
+  if (!ops.empty() && rccl_group(ops)) { free_all(); return -1; }
+  for (int i = 0; i < n; ++i) {
+    HIPC(hipSetDevice(coo[i]->ctx->device));
+    HIPC(hipStreamSynchronize(coo[i]->ctx->s_main));
+  }
+  // 5. swap in the new lists
+  for (int i = 0; i < n; ++i) {
+    pa_coo* C = coo[i];
+    CooSide& d = sd[i];
+    HIPC(hipSetDevice(C->ctx->device));
+    dev_free(C->d_I);
+    dev_free(C->d_J);
+    dev_free(C->d_V);
+    C->d_I = d.nI;
+    C->d_J = d.nJ;
+    C->d_V = d.nV;
+    C->n = d.nn;
+    d.nI = nullptr;
+    d.nJ = nullptr;
+    d.nV = nullptr;
+  }
+  free_all();
+  return 0;
+}
+
+// assemble!(I, J, V, rows) (to_ghosts = false: ghost rows' triplets to their
+// owners) and exchange!(I, J, V, rows) (to_ghosts = true: owners' triplets
+// to the ghost holders) over the n parts of this process
+int coo_send_all(bool to_ghosts, int n, pa_coo* const coo[], const pa_index* const rows[], pa_xchg* const xg[]) {
+  const std::string who = to_ghosts ? "exchange!" : "assemble!";
+  CHECK_ARG(n >= 1 && coo && rows && xg && coo[0], "null argument");
+  const int dt = coo[0]->dtype;
+  for (int i = 0; i < n; ++i) {
+    CHECK_ARG(coo[i] && rows[i] && xg[i], "null handle");
+    CHECK_ARG(coo[i]->dtype == dt, who + ": element types differ across parts");
+    CHECK_ARG(coo[i]->ctx == rows[i]->ctx && xg[i]->ctx == rows[i]->ctx, who + ": COO, rows and exchanger of different parts");
+    CHECK_ARG(rows[i]->has_gids, who + "(I,J,V,rows): rows needs its global ids on the device (pa_index_set_gids)");
+    CHECK_ARG(xg[i]->max_lid < rows[i]->nlids, who + ": the exchanger's lids exceed rows' local ids");
+  }
+  TuneScope ts(coo[0]->ctx);
+  std::vector<CooSide> sd(n);
+  // 1. assemble!: group the triplets of rows owned elsewhere by owner, zero
+  // them locally; exchange!: group the triplets of rows held elsewhere as
+  // ghosts by (last) holder, zero the unsent ghost rows' values
+  for (int i = 0; i < n; ++i) {
+    pa_coo* C = coo[i];
+    pa_xchg* X = xg[i];
+    const pa_index* R = rows[i];
+    HIPC(hipSetDevice(C->ctx->device));
+    const int rc =
+        to_ghosts ? coo_exchange_pack(dt, C->n, C->d_I, C->d_J, C->d_V, R->d_sgid, R->d_slid, R->nlids,
+                                      R->h_lid_to_ohid, (int)X->parts_snd.size(), X->d_lids_snd, X->ptrs_snd,
+                                      &sd[i].sI, &sd[i].sJ, &sd[i].sV, &sd[i].cnt, C->ctx->s_main)
+                  : coo_assemble_pack(dt, C->n, C->d_I, C->d_J, C->d_V, R->d_sgid, R->d_slid, R->nlids,
+                                      R->h_lid_to_ohid, (int)X->parts_rcv.size(), X->d_lids_rcv, X->ptrs_rcv,
+                                      &sd[i].sI, &sd[i].sJ, &sd[i].sV, &sd[i].cnt, C->ctx->s_main);
+    if (rc) {
+      coo_free_sides(n, coo, sd);
+      if (rc < 0) PA_FAIL(who + "(I,J,V,rows): device pass failed");
+      if (rc == 2) PA_FAIL("assemble!(I,J,V,rows): a ghost row's owner is not in the exchanger's parts_rcv (KeyError)");
+      PA_FAIL("to_lids!: a row global id is not a local id of rows (KeyError)");
+    }
+  }
+  return coo_move_segments(who.c_str(), n, coo, xg, sd, to_ghosts);
+}
 }  // namespace
 
 extern "C" {
@@ -2791,203 +3053,11 @@ int pa_coo_download(const pa_coo* C, int64_t* I, int64_t* J, void* V) {
 }
 
 int pa_coo_assemble_all(int n, pa_coo* const coo[], const pa_index* const rows[], pa_xchg* const xg[]) {
-  CHECK_ARG(n >= 1 && coo && rows && xg && coo[0], "null argument");
-  TuneScope ts(coo[0]->ctx);
-  const int dt = coo[0]->dtype;
-  const size_t S = dtype_size(dt);
-  for (int i = 0; i < n; ++i) {
-    CHECK_ARG(coo[i] && rows[i] && xg[i], "null handle");
-    CHECK_ARG(coo[i]->dtype == dt, "assemble!: element types differ across parts");
-    CHECK_ARG(coo[i]->ctx == rows[i]->ctx && xg[i]->ctx == rows[i]->ctx, "assemble!: COO, rows and exchanger of different parts");
-    CHECK_ARG(rows[i]->has_gids, "assemble!(I,J,V,rows): rows needs its global ids on the device (pa_index_set_gids)");
-    CHECK_ARG(xg[i]->max_lid < rows[i]->nlids, "assemble!: the exchanger's lids exceed rows' local ids");
-  }
-  // per part: the sent triplets (segments in parts_rcv order), counts and
-  // offsets; the received counts (parts_snd order); the new arrays
-  struct Side {
-    int64_t *sI = nullptr, *sJ = nullptr;
-    void* sV = nullptr;
-    std::vector<int64_t> cnt, off, rcnt, roff;
-    int64_t *nI = nullptr, *nJ = nullptr;
-    void* nV = nullptr;
-    int64_t nn = 0;
-  };
-  std::vector<Side> sd(n);
-  auto free_all = [&]() {
-    for (int i = 0; i < n; ++i) {
-      (void)hipSetDevice(coo[i]->ctx->device);
-      for (void* p : {(void*)sd[i].sI, (void*)sd[i].sJ, sd[i].sV, (void*)sd[i].nI, (void*)sd[i].nJ, sd[i].nV})
-        if (p) (void)hipFree(p);
-      sd[i] = Side{};
-    }
-  };
-  // 1. group the triplets of rows owned elsewhere by owner, zero them locally
-  for (int i = 0; i < n; ++i) {
-    pa_coo* C = coo[i];
-    pa_xchg* X = xg[i];
-    const pa_index* R = rows[i];
-    HIPC(hipSetDevice(C->ctx->device));
-    const int rc = coo_assemble_pack(dt, C->n, C->d_I, C->d_J, C->d_V, R->d_sgid, R->d_slid, R->nlids,
-                                     R->h_lid_to_ohid, (int)X->parts_rcv.size(), X->d_lids_rcv, X->ptrs_rcv,
-                                     &sd[i].sI, &sd[i].sJ, &sd[i].sV, &sd[i].cnt, C->ctx->s_main);
-    if (rc) {
-      free_all();
-      if (rc < 0) PA_FAIL("assemble!(I,J,V,rows): device pass failed");
-      if (rc == 2) PA_FAIL("assemble!(I,J,V,rows): a ghost row's owner is not in the exchanger's parts_rcv (KeyError)");
-      PA_FAIL("to_lids!: a row global id is not a local id of rows (KeyError)");
-    }
-    sd[i].off.assign(sd[i].cnt.size() + 1, 0);
-    for (size_t k = 0; k < sd[i].cnt.size(); ++k) sd[i].off[k + 1] = sd[i].off[k] + sd[i].cnt[k];
-  }
-  // 2. the counts each part receives, per entry of its parts_snd
-  LocalSet L = local_set(n, xg);
-  bool remote = false;
-  for (int i = 0; i < n; ++i) {
-    pa_xchg* X = xg[i];
-    sd[i].rcnt.assign(X->parts_snd.size(), 0);
-    for (size_t j = 0; j < X->parts_snd.size(); ++j) {
-      const int jj = L.find(X->parts_snd[j]);
-      if (jj < 0) { remote = true; continue; }
-      const auto& q = xg[jj]->parts_rcv;
-      const auto it = std::find(q.begin(), q.end(), X->ctx->part);
-      if (it == q.end()) { free_all(); PA_FAIL("assemble!: exchanger mismatch (a part in parts_snd does not list this part in parts_rcv)"); }
-      sd[i].rcnt[j] = sd[jj].cnt[it - q.begin()];
-    }
-    for (int32_t q : X->parts_rcv)
-      if (L.find(q) < 0) remote = true;
-  }
-  if (remote) {  // counts of the other processes' parts: one RCCL group of 8 B messages
-    std::vector<int64_t*> dsc(n, nullptr), drc(n, nullptr);
-    auto free_cnt = [&]() {
-      for (int i = 0; i < n; ++i) { (void)hipSetDevice(coo[i]->ctx->device); dev_free(dsc[i]); dev_free(drc[i]); }
-    };
-    std::vector<P2P> ops;
-    for (int i = 0; i < n; ++i) {
-      pa_xchg* X = xg[i];
-      pa_ctx* c = X->ctx;
-      if (!c->comm) { free_cnt(); free_all(); PA_FAIL("assemble!: a neighbour is not held by this process and no RCCL communicator was initialised"); }
-      HIPC(hipSetDevice(c->device));
-      if (dev_upload(&dsc[i], sd[i].cnt)) { free_cnt(); free_all(); return -1; }
-      if (!X->parts_snd.empty()) HIPC(hipMalloc((void**)&drc[i], X->parts_snd.size() * 8));
-      for (size_t k = 0; k < X->parts_rcv.size(); ++k)
-        if (L.find(X->parts_rcv[k]) < 0)
-          ops.push_back({c->part, X->parts_rcv[k], true, (char*)(dsc[i] + k), 8, c->peer_rank(X->parts_rcv[k]),
-                         (ncclComm_t)c->comm, c->s_main});
-      for (size_t j = 0; j < X->parts_snd.size(); ++j)
-        if (L.find(X->parts_snd[j]) < 0)
-          ops.push_back({X->parts_snd[j], c->part, false, (char*)(drc[i] + j), 8, c->peer_rank(X->parts_snd[j]),
-                         (ncclComm_t)c->comm, c->s_main});
-    }
-    if (rccl_group(ops)) { free_cnt(); free_all(); return -1; }
-    for (int i = 0; i < n; ++i) {
-      pa_xchg* X = xg[i];
-      HIPC(hipSetDevice(X->ctx->device));
-      HIPC(hipStreamSynchronize(X->ctx->s_main));
-      std::vector<int64_t> got(X->parts_snd.size());
-      if (!got.empty()) HIPC(hipMemcpy(got.data(), drc[i], got.size() * 8, hipMemcpyDeviceToHost));
-      for (size_t j = 0; j < X->parts_snd.size(); ++j)
-        if (L.find(X->parts_snd[j]) < 0) sd[i].rcnt[j] = got[j];
-    }
-    free_cnt();
-  }
-  // 3. the new lists: the local triplets (sent ones now zero), then the
-  // received segments in parts_snd order (Interfaces.jl:2470-2486)
-  for (int i = 0; i < n; ++i) {
-    pa_coo* C = coo[i];
-    Side& d = sd[i];
-    d.roff.assign(d.rcnt.size() + 1, 0);
-    for (size_t j = 0; j < d.rcnt.size(); ++j) d.roff[j + 1] = d.roff[j] + d.rcnt[j];
-    d.nn = C->n + d.roff.back();
-    HIPC(hipSetDevice(C->ctx->device));
-    if (d.nn > 0) {
-      hipError_t e = hipMalloc((void**)&d.nI, d.nn * 8);
-      if (e == hipSuccess) e = hipMalloc((void**)&d.nJ, d.nn * 8);
-      if (e == hipSuccess) e = hipMalloc(&d.nV, d.nn * S);
-      if (e != hipSuccess) { free_all(); HIPC(e); }
-    }
-    if (C->n > 0) {
-      hipStream_t st = C->ctx->s_main;
-      HIPC(hipMemcpyAsync(d.nI, C->d_I, C->n * 8, hipMemcpyDeviceToDevice, st));
-      HIPC(hipMemcpyAsync(d.nJ, C->d_J, C->n * 8, hipMemcpyDeviceToDevice, st));
-      HIPC(hipMemcpyAsync(d.nV, C->d_V, C->n * S, hipMemcpyDeviceToDevice, st));
-    }
-  }
-  for (int i = 0; i < n; ++i) {  // every pack has finished before any part reads it
-    HIPC(hipSetDevice(coo[i]->ctx->device));
-    HIPC(hipStreamSynchronize(coo[i]->ctx->s_main));
-  }
-  // 4. the segments: device copies between the parts of this process, one
-  // RCCL group (I, J, V per segment) for the others
-  std::vector<P2P> ops;
-  for (int i = 0; i < n; ++i) {
-    pa_xchg* X = xg[i];
-    pa_ctx* c = X->ctx;
-    Side& d = sd[i];
-    HIPC(hipSetDevice(c->device));
-    for (size_t j = 0; j < X->parts_snd.size(); ++j) {
-      const int64_t m = d.rcnt[j];
-      if (m == 0) continue;
-      const int64_t at = coo[i]->n + d.roff[j];
-      const int jj = L.find(X->parts_snd[j]);
-      if (jj < 0) {
-        const int q = X->parts_snd[j], pr = c->peer_rank(q);
-        ncclComm_t cm = (ncclComm_t)c->comm;
-        ops.push_back({q, c->part, false, (char*)(d.nI + at), (size_t)m * 8, pr, cm, c->s_main});
-        ops.push_back({q, c->part, false, (char*)(d.nJ + at), (size_t)m * 8, pr, cm, c->s_main});
-        ops.push_back({q, c->part, false, (char*)d.nV + at * S, (size_t)m * S, pr, cm, c->s_main});
-        continue;
-      }
-      const auto& qr = xg[jj]->parts_rcv;
-      const int64_t k = std::find(qr.begin(), qr.end(), c->part) - qr.begin();
-      const Side& src = sd[jj];
-      const int64_t from = src.off[k];
-      const int sdev = xg[jj]->ctx->device;
-      if (sdev == c->device) {
-        HIPC(hipMemcpyAsync(d.nI + at, src.sI + from, m * 8, hipMemcpyDeviceToDevice, c->s_main));
-        HIPC(hipMemcpyAsync(d.nJ + at, src.sJ + from, m * 8, hipMemcpyDeviceToDevice, c->s_main));
-        HIPC(hipMemcpyAsync((char*)d.nV + at * S, (const char*)src.sV + from * S, m * S, hipMemcpyDeviceToDevice,
-                            c->s_main));
-      } else {
-        HIPC(hipMemcpyPeerAsync(d.nI + at, c->device, src.sI + from, sdev, m * 8, c->s_main));
-        HIPC(hipMemcpyPeerAsync(d.nJ + at, c->device, src.sJ + from, sdev, m * 8, c->s_main));
-        HIPC(hipMemcpyPeerAsync((char*)d.nV + at * S, c->device, (const char*)src.sV + from * S, sdev, m * S,
-                                c->s_main));
-      }
-    }
-    for (size_t k = 0; k < X->parts_rcv.size(); ++k) {
-      const int64_t m = d.cnt[k];
-      const int q = X->parts_rcv[k];
-      if (m == 0 || L.find(q) >= 0) continue;
-      const int pr = c->peer_rank(q);
-      ncclComm_t cm = (ncclComm_t)c->comm;
-      ops.push_back({c->part, q, true, (char*)(d.sI + d.off[k]), (size_t)m * 8, pr, cm, c->s_main});
-      ops.push_back({c->part, q, true, (char*)(d.sJ + d.off[k]), (size_t)m * 8, pr, cm, c->s_main});
-      ops.push_back({c->part, q, true, (char*)d.sV + d.off[k] * S, (size_t)m * S, pr, cm, c->s_main});
-    }
-  }
-  if (!ops.empty() && rccl_group(ops)) { free_all(); return -1; }
-  for (int i = 0; i < n; ++i) {
-    HIPC(hipSetDevice(coo[i]->ctx->device));
-    HIPC(hipStreamSynchronize(coo[i]->ctx->s_main));
-  }
-  // 5. swap in the new lists
-  for (int i = 0; i < n; ++i) {
-    pa_coo* C = coo[i];
-    Side& d = sd[i];
-    HIPC(hipSetDevice(C->ctx->device));
-    dev_free(C->d_I);
-    dev_free(C->d_J);
-    dev_free(C->d_V);
-    C->d_I = d.nI;
-    C->d_J = d.nJ;
-    C->d_V = d.nV;
-    C->n = d.nn;
-    d.nI = nullptr;
-    d.nJ = nullptr;
-    d.nV = nullptr;
-  }
-  free_all();
-  return 0;
+  return coo_send_all(false, n, coo, rows, xg);
+}
+
+int pa_coo_exchange_all(int n, pa_coo* const coo[], const pa_index* const rows[], pa_xchg* const xg[]) {
+  return coo_send_all(true, n, coo, rows, xg);
 }
 
 // the CSC nz → value map on the host (built on the device by pa_mat_from_coo)

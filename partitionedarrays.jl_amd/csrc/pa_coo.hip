@@ -632,9 +632,10 @@ __global__ void k_key_first(int64_t n, const uint64_t* __restrict__ key, int64_t
     if (t == 0 || key[t] != key[t - 1]) first[key[t]] = t;
 }
 
-// the nr sent triplets in segment order: sI/sJ/sV[t] = I/J/V[idx[t]], and
-// the local value becomes zero(v) (the entry stays in the local list)
-template <typename T>
+// the nr sent triplets in segment order: sI/sJ/sV[t] = I/J/V[idx[t]]; with
+// ZERO_SRC (assemble!) the local value becomes zero(v) (the entry stays in
+// the local list), without it (exchange!) the local entry is left as it is
+template <typename T, bool ZERO_SRC>
 __global__ void k_coo_pack(int64_t nr, const int64_t* __restrict__ idx, const int64_t* __restrict__ I,
                            const int64_t* __restrict__ J, T* __restrict__ V, int64_t* __restrict__ sI,
                            int64_t* __restrict__ sJ, T* __restrict__ sV) {
@@ -643,8 +644,63 @@ __global__ void k_coo_pack(int64_t nr, const int64_t* __restrict__ idx, const in
     sI[t] = I[k];
     sJ[t] = J[k];
     sV[t] = V[k];
-    V[k] = zero_of<T>();
+    if (ZERO_SRC) V[k] = zero_of<T>();
   }
+}
+
+template <typename T>
+static void coo_pack_t(int64_t nr, const int64_t* idx, const int64_t* I, const int64_t* J, void* V, bool zero_src,
+                       int64_t* sI, int64_t* sJ, void* sV, hipStream_t st) {
+  auto kern = zero_src ? k_coo_pack<T, true> : k_coo_pack<T, false>;
+  hipLaunchKernelGGL(kern, grid1(nr), dim3(256), 0, st, nr, idx, I, J, (T*)V, sI, sJ, (T*)sV);
+}
+
+// The common tail of the two send sides: key[k] = 0 (stays) or 1 + segment,
+// idx[k] = k.  Sorts by key (stable: input order inside a segment), counts
+// the segments into cnt[0..nseg) and copies the sent triplets out, segment
+// after segment, into *sI, *sJ, *sV (device, owned by the caller).  key and
+// idx may be reallocated by the sort.
+static hipError_t coo_pack_by_key(int dtype, int64_t n, const int64_t* I, const int64_t* J, void* V, uint64_t*& key,
+                                  int64_t*& idx, int nseg, bool zero_src, int64_t** sI, int64_t** sJ, void** sV,
+                                  std::vector<int64_t>* cnt, hipStream_t st) {
+  const size_t S = dtype_size(dtype);
+  int64_t* first = nullptr;
+  std::vector<int64_t> hfirst(nseg + 2, -1);
+  int64_t nloc = n;
+  hipError_t e = sort_pairs(key, idx, n, bits_for((uint64_t)nseg + 1), st);
+  if (e == hipSuccess) e = hipMalloc((void**)&first, (nseg + 2) * 8);
+  if (e == hipSuccess) e = hipMemsetAsync(first, 0xff, (nseg + 2) * 8, st);
+  if (e != hipSuccess) goto done;
+  hipLaunchKernelGGL(k_key_first, grid1(n), dim3(256), 0, st, n, key, first);
+  e = hipMemcpyAsync(hfirst.data(), first, (nseg + 1) * 8, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) goto done;
+  {
+    // end of key q = start of the next present key, or n
+    hfirst[nseg + 1] = n;
+    std::vector<int64_t> start(nseg + 2, n);
+    for (int q = nseg; q >= 0; --q) start[q] = hfirst[q] >= 0 ? hfirst[q] : start[q + 1];
+    nloc = start[1];
+    for (int q = 0; q < nseg; ++q) (*cnt)[q] = start[q + 2] - start[q + 1];
+  }
+  if (n - nloc > 0) {
+    const int64_t nr = n - nloc;
+    e = hipMalloc((void**)sI, nr * 8);
+    if (e == hipSuccess) e = hipMalloc((void**)sJ, nr * 8);
+    if (e == hipSuccess) e = hipMalloc(sV, nr * S);
+    if (e != hipSuccess) goto done;
+    switch (dtype) {
+      case PA_F32: coo_pack_t<float>(nr, idx + nloc, I, J, V, zero_src, *sI, *sJ, *sV, st); break;
+      case PA_F64: coo_pack_t<double>(nr, idx + nloc, I, J, V, zero_src, *sI, *sJ, *sV, st); break;
+      case PA_C64: coo_pack_t<c64>(nr, idx + nloc, I, J, V, zero_src, *sI, *sJ, *sV, st); break;
+      case PA_C128: coo_pack_t<c128>(nr, idx + nloc, I, J, V, zero_src, *sI, *sJ, *sV, st); break;
+    }
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+  }
+done:
+  if (first) (void)hipFree(first);
+  return e;
 }
 
 // One part's send side.  Outputs (device, owned by the caller): *sI, *sJ,
@@ -656,19 +712,16 @@ int coo_assemble_pack(int dtype, int64_t n, const int64_t* I, const int64_t* J, 
                       const int32_t* d_lids_rcv,
                       const std::vector<int64_t>& ptrs_rcv, int64_t** sI, int64_t** sJ, void** sV,
                       std::vector<int64_t>* cnt, hipStream_t st) {
-  const size_t S = dtype_size(dtype);
   *sI = nullptr; *sJ = nullptr; *sV = nullptr;
   cnt->assign(nseg, 0);
   if (n <= 0) return 0;
   hipError_t e = hipSuccess;
   int32_t* sol = nullptr;
-  int64_t *dptrs = nullptr, *idx = nullptr, *first = nullptr;
+  int64_t *dptrs = nullptr, *idx = nullptr;
   uint64_t* key = nullptr;
   int* bad = nullptr;
   int hbad = 0, rc = 0;
-  std::vector<int64_t> hfirst(nseg + 2, -1);
   const int64_t nslots = ptrs_rcv.empty() ? 0 : ptrs_rcv.back();
-  int64_t nloc = n;
   {
     // -1: owned lid, -2: ghost lid (k_seg_of_lid then sets its segment)
     std::vector<int32_t> hs(nl > 0 ? nl : 1, -1);
@@ -691,41 +744,120 @@ int coo_assemble_pack(int dtype, int64_t n, const int64_t* I, const int64_t* J, 
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) goto done;
   if (hbad) { rc = hbad; goto done; }  // 1: unknown gid, 2: ghost row without a segment
-  e = sort_pairs(key, idx, n, bits_for((uint64_t)nseg + 1), st);  // stable: input order inside a segment
-  if (e == hipSuccess) e = hipMalloc((void**)&first, (nseg + 2) * 8);
-  if (e == hipSuccess) e = hipMemsetAsync(first, 0xff, (nseg + 2) * 8, st);
+  e = coo_pack_by_key(dtype, n, I, J, V, key, idx, nseg, true, sI, sJ, sV, cnt, st);
+done:
+  for (void* p : {(void*)sol, (void*)dptrs, (void*)idx, (void*)key, (void*)bad})
+    if (p) (void)hipFree(p);
+  if (e != hipSuccess || rc) {
+    for (void** p : {(void**)sI, (void**)sJ, sV})
+      if (*p) { (void)hipFree(*p); *p = nullptr; }
+    return e != hipSuccess ? -1 : rc;
+  }
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// async_exchange!(I, J, V, rows) (Interfaces.jl:2494-2592) on the device, the
+// mirror of the assembly above: the triplets of the rows that other parts
+// hold as ghosts are copied out per neighbour (segments in
+// rows.exchanger.parts_snd order, input order inside each) and stay in the
+// local list unchanged; the host side (pa_api.cpp) moves the segments to the
+// ghost holders, which append them in parts_rcv order.
+
+// snd_of_lid[l] (0 for an owned lid, -1 for a ghost lid on entry) becomes
+// 1 + the last segment of lids_snd that lists l: the reference's loop
+// `lid_to_i[lid] = i` (2514-2520) overwrites, so a lid that several
+// neighbours hold as a ghost keeps the last of them.  Slots of different
+// segments may name the same lid, hence the atomic max and not a store.
+__global__ void k_snd_seg_of_lid(int64_t nslots, const int32_t* __restrict__ lids_snd,
+                                 const int64_t* __restrict__ ptrs, int nseg, int32_t* __restrict__ snd_of_lid) {
+  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < nslots; t += (int64_t)gridDim.x * blockDim.x) {
+    int lo = 0, hi = nseg;  // last segment whose start <= t
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (ptrs[mid] <= t) lo = mid; else hi = mid;
+    }
+    atomicMax(&snd_of_lid[lids_snd[t]], lo + 1);
+  }
+}
+
+// key[k] = 1 + the send segment of the row's lid, or 0 when no neighbour
+// holds the row; then a ghost row's value becomes zero(Tv) (2529-2530: an
+// exact +0, not v*0) and an owned row's triplet is left alone.  *bad = 1 for
+// a row gid that is not a local id of rows (the KeyError of to_lids!).
+template <typename T>
+__global__ void k_coo_xseg(int64_t n, const int64_t* __restrict__ I, T* __restrict__ V,
+                           const uint64_t* __restrict__ sgid, const int64_t* __restrict__ slid, int64_t nl,
+                           const int32_t* __restrict__ snd_of_lid, uint64_t* __restrict__ key,
+                           int64_t* __restrict__ idx, int* __restrict__ bad) {
+  for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t l = gid_lookup(I[k], sgid, slid, nl);
+    const int32_t sg = l < 0 ? 0 : snd_of_lid[l];
+    if (l < 0) *bad = 1;
+    else if (sg < 0) V[k] = zero_of<T>();
+    key[k] = sg > 0 ? (uint64_t)sg : 0;
+    idx[k] = k;
+  }
+}
+
+template <typename T>
+static void coo_xseg_t(int64_t n, const int64_t* I, void* V, const uint64_t* sgid, const int64_t* slid, int64_t nl,
+                       const int32_t* snd_of_lid, uint64_t* key, int64_t* idx, int* bad, hipStream_t st) {
+  hipLaunchKernelGGL(k_coo_xseg<T>, grid1(n), dim3(256), 0, st, n, I, (T*)V, sgid, slid, nl, snd_of_lid, key, idx,
+                     bad);
+}
+
+// One part's send side of exchange!.  Outputs as coo_assemble_pack: *sI, *sJ,
+// *sV (the sent triplets, segment after segment; device, owned by the
+// caller) and cnt[0..nseg) on the host, nseg = length(parts_snd).  Every lid
+// of d_lids_snd is below nl (checked by the caller).  Returns 1 when a row
+// gid is not a local id of rows (KeyError); ghost rows met before that may
+// already hold zero, as the reference leaves I half converted.
+int coo_exchange_pack(int dtype, int64_t n, const int64_t* I, const int64_t* J, void* V, const uint64_t* sgid,
+                      const int64_t* slid, int64_t nl, const std::vector<int32_t>& lid_to_ohid, int nseg,
+                      const int32_t* d_lids_snd, const std::vector<int64_t>& ptrs_snd, int64_t** sI, int64_t** sJ,
+                      void** sV, std::vector<int64_t>* cnt, hipStream_t st) {
+  *sI = nullptr; *sJ = nullptr; *sV = nullptr;
+  cnt->assign(nseg, 0);
+  if (n <= 0) return 0;
+  hipError_t e = hipSuccess;
+  int32_t* sol = nullptr;
+  int64_t *dptrs = nullptr, *idx = nullptr;
+  uint64_t* key = nullptr;
+  int* bad = nullptr;
+  int hbad = 0, rc = 0;
+  const int64_t nslots = ptrs_snd.empty() ? 0 : ptrs_snd.back();
+  {
+    // 0: owned lid, -1: ghost lid (k_snd_seg_of_lid then raises the listed ones)
+    std::vector<int32_t> hs(nl > 0 ? nl : 1, 0);
+    for (int64_t l = 0; l < nl; ++l) hs[l] = lid_to_ohid[l] > 0 ? 0 : -1;
+    e = hipMalloc((void**)&sol, hs.size() * 4);
+    if (e == hipSuccess) e = copy_sync(sol, hs.data(), hs.size() * 4, hipMemcpyHostToDevice, st);
+  }
+  if (e == hipSuccess && nslots > 0) e = hipMalloc((void**)&dptrs, ptrs_snd.size() * 8);
+  if (e == hipSuccess && nslots > 0)
+    e = hipMemcpyAsync(dptrs, ptrs_snd.data(), ptrs_snd.size() * 8, hipMemcpyHostToDevice, st);
   if (e != hipSuccess) goto done;
-  hipLaunchKernelGGL(k_key_first, grid1(n), dim3(256), 0, st, n, key, first);
-  e = hipMemcpyAsync(hfirst.data(), first, (nseg + 1) * 8, hipMemcpyDeviceToHost, st);
+  if (nslots > 0)
+    hipLaunchKernelGGL(k_snd_seg_of_lid, grid1(nslots), dim3(256), 0, st, nslots, d_lids_snd, dptrs, nseg, sol);
+  e = hipMalloc((void**)&key, n * 8);
+  if (e == hipSuccess) e = hipMalloc((void**)&idx, n * 8);
+  if (e == hipSuccess) e = hipMalloc((void**)&bad, sizeof(int));
+  if (e == hipSuccess) e = hipMemsetAsync(bad, 0, sizeof(int), st);
+  if (e != hipSuccess) goto done;
+  switch (dtype) {
+    case PA_F32: coo_xseg_t<float>(n, I, V, sgid, slid, nl, sol, key, idx, bad, st); break;
+    case PA_F64: coo_xseg_t<double>(n, I, V, sgid, slid, nl, sol, key, idx, bad, st); break;
+    case PA_C64: coo_xseg_t<c64>(n, I, V, sgid, slid, nl, sol, key, idx, bad, st); break;
+    case PA_C128: coo_xseg_t<c128>(n, I, V, sgid, slid, nl, sol, key, idx, bad, st); break;
+  }
+  e = hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) goto done;
-  {
-    // end of key q = start of the next present key, or n
-    hfirst[nseg + 1] = n;
-    std::vector<int64_t> start(nseg + 2, n);
-    for (int q = nseg; q >= 0; --q) start[q] = hfirst[q] >= 0 ? hfirst[q] : start[q + 1];
-    nloc = start[1];
-    for (int q = 0; q < nseg; ++q) (*cnt)[q] = start[q + 2] - start[q + 1];
-  }
-  if (n - nloc > 0) {
-    const int64_t nr = n - nloc;
-    e = hipMalloc((void**)sI, nr * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)sJ, nr * 8);
-    if (e == hipSuccess) e = hipMalloc(sV, nr * S);
-    if (e != hipSuccess) goto done;
-#define PA_PK(T) hipLaunchKernelGGL(k_coo_pack<T>, grid1(nr), dim3(256), 0, st, nr, idx + nloc, I, J, (T*)V, *sI, *sJ, (T*)*sV)
-    switch (dtype) {
-      case PA_F32: PA_PK(float); break;
-      case PA_F64: PA_PK(double); break;
-      case PA_C64: PA_PK(c64); break;
-      case PA_C128: PA_PK(c128); break;
-    }
-#undef PA_PK
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-  }
+  if (hbad) { rc = 1; goto done; }
+  e = coo_pack_by_key(dtype, n, I, J, V, key, idx, nseg, false, sI, sJ, sV, cnt, st);
 done:
-  for (void* p : {(void*)sol, (void*)dptrs, (void*)idx, (void*)first, (void*)key, (void*)bad})
+  for (void* p : {(void*)sol, (void*)dptrs, (void*)idx, (void*)key, (void*)bad})
     if (p) (void)hipFree(p);
   if (e != hipSuccess || rc) {
     for (void** p : {(void**)sI, (void**)sJ, sV})

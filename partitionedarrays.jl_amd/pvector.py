@@ -300,9 +300,14 @@ def _hs(objs):
     return _lib.ptr_array([o.h if o is not None else None for o in objs])
 
 
-def exchange_(v):
+def exchange_(v, rows: PRange = None):
     """exchange!(v) (Interfaces.jl:453-458, 2071-2075): owner → ghost values.
-    For a PSparseMatrix: exchange!(A) over nonzeros(A) (2375-2381)."""
+    For a PSparseMatrix: exchange!(A) over nonzeros(A) (2375-2381).  For a
+    COO and its rows: exchange!(I, J, V, rows) (2494-2592) on the device."""
+    if isinstance(v, COO):
+        if rows is None:
+            raise TypeError("exchange!(I, J, V, rows): the rows PRange is required")
+        return _coo_all("pa_coo_exchange_all", v, rows)
     if isinstance(v, PSparseMatrix):
         return _mat_exchange(v, _lib.PA_REPLACE, 0, 0)
     ctxs = contexts(v.values)
@@ -337,16 +342,20 @@ class COO:
         return map_parts(lambda c: c.download()[1], self.values)
 
 
-def _assemble_coo(coo: COO, rows: PRange) -> COO:
-    """async_assemble!(I, J, V, rows) + wait (Interfaces.jl:2406-2492) on the
-    device (pa_coo_assemble_all): triplets of rows owned elsewhere go to the
-    owner (local value set to zero, entry kept), received ones are appended
-    in rows.exchanger.parts_snd order."""
+def _coo_all(entry: str, coo: COO, rows: PRange) -> COO:
+    """pa_coo_assemble_all — async_assemble!(I, J, V, rows) + wait
+    (Interfaces.jl:2406-2492) on the device: triplets of rows owned elsewhere
+    go to the owner (local value set to zero, entry kept), received ones are
+    appended in rows.exchanger.parts_snd order — or pa_coo_exchange_all —
+    async_exchange!(I, J, V, rows) + wait (2494-2592): triplets of rows that
+    other parts hold as ghosts are copied to the last such part in
+    rows.exchanger.parts_snd order (local entry kept), unsent ghost rows'
+    values become zero, received ones are appended in parts_rcv order."""
     ctxs = contexts(rows.partition)
     pids = rows.partition.part_ids
     idx = [device_index_gids(c, rows.partition.local(p)) for c, p in zip(ctxs, pids)]
     xg = [device_exchanger(c, rows.exchanger, p) for c, p in zip(ctxs, pids)]
-    _lib.call("pa_coo_assemble_all", len(ctxs), _hs(coo.values.parts), _hs(idx), _hs(xg))
+    _lib.call(entry, len(ctxs), _hs(coo.values.parts), _hs(idx), _hs(xg))
     return coo
 
 
@@ -359,7 +368,7 @@ def assemble_(v, rows: PRange = None):
     if isinstance(v, COO):
         if rows is None:
             raise TypeError("assemble!(I, J, V, rows): the rows PRange is required")
-        return _assemble_coo(v, rows)
+        return _coo_all("pa_coo_assemble_all", v, rows)
     if isinstance(v, PSparseMatrix):
         return _mat_exchange(v, _lib.PA_ADD, 1, 1)
     ctxs = contexts(v.values)
