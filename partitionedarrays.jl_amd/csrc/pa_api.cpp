@@ -92,12 +92,12 @@ const Knobs kDefaults = {
     /*halo_barrier*/ 1, /*tri_order*/ 1, /*side_tail*/ 1, /*f32_rows*/ 0, /*tri_pack*/ 7, /*uniform*/ 1};
 // COO → CSC → SELL on the device (pa_coo.hip)
 int coo_compress(int dtype, int index_bytes, int64_t m, int64_t ncols, int64_t n, const void* dI, const void* dJ,
-                 const void* dV, int csr, int64_t* nu_out, int32_t** crow, int32_t** ccol, void** cval,
-                 int64_t** colptr, hipStream_t st, hipError_t* err_out);
+                 const void* dV, int csr, int64_t* nu_out, DevBuf<int32_t>& crow, DevBuf<int32_t>& ccol,
+                 DevBuf<void>& cval, DevBuf<int64_t>& colptr, hipStream_t st, hipError_t* err);
 int coo_row_order(int64_t nu, const int32_t* crow, const int32_t* ccol, const int32_t* rl2o, const int32_t* cl2o,
-                  int64_t nrows, int64_t noids_c, int64_t ncols, int H, uint64_t** key2, int64_t** idx2,
-                  int64_t** rowptr, int64_t** gflag, int64_t** grank, int32_t** slen, int32_t** sghost,
-                  int64_t* nnz_out, int64_t* ngh_out, hipStream_t st, hipError_t* err_out);
+                  int64_t nrows, int64_t noids_c, int64_t ncols, int H, DevBuf<uint64_t>& key2, DevBuf<int64_t>& idx2,
+                  DevBuf<int64_t>& rowptr, DevBuf<int64_t>& gflag, DevBuf<int64_t>& grank, DevBuf<int32_t>& slen,
+                  DevBuf<int32_t>& sghost, int64_t* nnz_out, int64_t* ngh_out, hipStream_t st, hipError_t* err);
 void coo_slices(int64_t ns, int64_t nrows, int H, const int64_t* rowptr, const uint64_t* key2, int64_t ncols,
                 int64_t noids_c, const int32_t* lidx, int32_t* slen, int32_t* sghost, hipStream_t st);
 void coo_fill(int dtype, int64_t nnz, int64_t nu, const uint64_t* key2, const int64_t* idx2, const int64_t* rowptr,
@@ -107,18 +107,13 @@ void coo_fill(int dtype, int64_t nnz, int64_t nu, const uint64_t* key2, const in
 void launch_fill_i32(int64_t n, int32_t* a, int32_t v, hipStream_t st);
 void launch_spmv_long(const pa_mat* A, const void* x, void* y, const int32_t* ymap, bool has_alpha, int bmode,
                       const void* alpha, const void* beta, void* dotp, int64_t dot_base, hipStream_t st);
-int gid_table(int64_t n, const int64_t* d_lid_to_gid, uint64_t** sgid, int64_t** slid, hipStream_t st);
+int gid_table(int64_t n, const int64_t* d_lid_to_gid, DevBuf<uint64_t>& sgid, DevBuf<int64_t>& slid, hipStream_t st);
 int gids_to_lids(int64_t n, int64_t* ids, const uint64_t* sgid, const int64_t* slid, int64_t nl, hipStream_t st);
-int coo_assemble_pack(int dtype, int64_t n, const int64_t* I, const int64_t* J, void* V, const uint64_t* sgid,
-                      const int64_t* slid, int64_t nl, const std::vector<int32_t>& lid_to_ohid, int nseg,
-                      const int32_t* d_lids_rcv, const std::vector<int64_t>& ptrs_rcv, int64_t** sI, int64_t** sJ,
-                      void** sV, std::vector<int64_t>* cnt, hipStream_t st);
-int coo_exchange_pack(int dtype, int64_t n, const int64_t* I, const int64_t* J, void* V, const uint64_t* sgid,
-                      const int64_t* slid, int64_t nl, const std::vector<int32_t>& lid_to_ohid, int nseg,
-                      const int32_t* d_lids_snd, const std::vector<int64_t>& ptrs_snd, int64_t** sI, int64_t** sJ,
-                      void** sV, std::vector<int64_t>* cnt, hipStream_t st);
+int coo_send_pack(bool to_ghosts, int dtype, const CooList& in, const uint64_t* sgid, const int64_t* slid, int64_t nl,
+                  const std::vector<int32_t>& lid_to_ohid, const XchgSide& side, CooList* out,
+                  std::vector<int64_t>* cnt, hipStream_t st);
 int gids_first_touch(int64_t n, const int64_t* gids, const uint64_t* sgid, const int64_t* slid, int64_t nl,
-                     int64_t** out, int64_t* m_out, hipStream_t st);
+                     DevBuf<int64_t>& out, int64_t* m_out, hipStream_t st);
 // ev (optional): recorded on st when the kernel completes (one runtime call)
 void launch_pack(int dtype, int64_t n, const int32_t* lids, const void* v, void* buf,
                  hipStream_t st, hipEvent_t ev = nullptr);
@@ -237,18 +232,11 @@ int build_plan(const std::vector<int32_t>& lids, pa_combine_plan* plan) {
   plan->ntargets = (int64_t)target.size();
   plan->unique = plan->ntargets == n;
   if (!plan->unique) {
-    if (dev_upload(&plan->d_target, target)) return -1;
-    if (dev_upload(&plan->d_ptr, ptr)) return -1;
-    if (dev_upload(&plan->d_pos, pos)) return -1;
+    HIPC(plan->d_target.upload(target));
+    HIPC(plan->d_ptr.upload(ptr));
+    HIPC(plan->d_pos.upload(pos));
   }
   return 0;
-}
-
-void free_plan(pa_combine_plan& p) {
-  dev_free(p.d_target);
-  dev_free(p.d_ptr);
-  dev_free(p.d_pos);
-  p = pa_combine_plan{};
 }
 
 // Row-length histogram → long rows: a row is long when it has more than
@@ -908,23 +896,36 @@ LocalSet local_set(int n, H* const* hs) {
   return L;
 }
 
+// the segment of Q's from(dir) side addressed to `part`: its index m, or an error;
+// checks cnt against Q's segment length when cnt >= 0
+int peer_segment(const pa_xchg* Q, int dir, int part, int64_t cnt, int* m) {
+  const XchgSide& q = Q->from(dir);
+  const auto it = std::find(q.parts.begin(), q.parts.end(), part);
+  CHECK_ARG(it != q.parts.end(), "exchanger mismatch: a receiver lists a sender that does not send to it");
+  *m = (int)(it - q.parts.begin());
+  CHECK_ARG(cnt < 0 || cnt == q.ptrs[*m + 1] - q.ptrs[*m],
+            "exchanger mismatch: segment lengths differ (SequentialBackend.jl:187)");
+  return 0;
+}
+
+// the reference's name of the from(dir) list, for error texts (into(dir)'s: side_name(1 - dir))
+const char* side_name(int dir) { return dir ? "parts_rcv" : "parts_snd"; }
+
 uint64_t g_xchg_next_id = 1;
 
 // Pull table of receiver i for direction dir (see pa_pull): built once per
 // set of local senders; ok = false when a sender's device is not reachable
 // by peer access (then the staging copies below are used).  alt: the
-// forward table against the senders' second send buffers (d_buf_snd2, the
+// forward table against the senders' second send buffers (buf_snd2, the
 // barrier issue of spmv_impl).
 int build_pull(int i, int n, pa_xchg* const xg[], const LocalSet& L, int dtype, int dir, bool alt = false) {
   pa_xchg* X = xg[i];
   pa_ctx* c = X->ctx;
   pa_pull& P = alt ? X->pull_alt : X->pull[dir];
-  auto sender_buf = [&](const pa_xchg* Q) -> void* {
-    return alt ? Q->d_buf_snd2 : (dir == 0 ? Q->d_buf_snd : Q->d_buf_rcv);
-  };
-  const auto& prcv = dir == 0 ? X->parts_rcv : X->parts_snd;
-  const auto& orcv = dir == 0 ? X->ptrs_rcv : X->ptrs_snd;
-  void* own = dir == 0 ? X->d_buf_rcv : X->d_buf_snd;
+  auto sender_buf = [&](const pa_xchg* Q) -> void* { return alt ? Q->buf_snd2 : Q->from(dir).buf; };
+  const auto& prcv = X->into(dir).parts;
+  const auto& orcv = X->into(dir).ptrs;
+  void* own = X->into(dir).buf;
   std::vector<const void*> key;
   key.push_back((const void*)(intptr_t)dtype_size(dtype));
   for (int32_t q : prcv) {
@@ -933,13 +934,10 @@ int build_pull(int i, int n, pa_xchg* const xg[], const LocalSet& L, int dtype, 
     key.push_back(j >= 0 ? sender_buf(xg[j]) : own);
   }
   if (P.built && P.key == key) return 0;
-  dev_free(P.d_bid);
-  dev_free(P.d_elem);
-  dev_free(P.d_bases);
+  HIPC(hipSetDevice(c->device));
   P = pa_pull{};
   P.built = true;
   P.key = key;
-  HIPC(hipSetDevice(c->device));
   std::vector<void*> bases;
   auto base_id = [&](void* b) {
     for (size_t t = 0; t < bases.size(); ++t)
@@ -959,13 +957,9 @@ int build_pull(int i, int n, pa_xchg* const xg[], const LocalSet& L, int dtype, 
       continue;
     }
     pa_xchg* Q = xg[j];
-    const auto& qsnd = dir == 0 ? Q->parts_snd : Q->parts_rcv;
-    const auto& qo = dir == 0 ? Q->ptrs_snd : Q->ptrs_rcv;
+    const auto& qo = Q->from(dir).ptrs;
     int m = -1;
-    for (size_t t = 0; t < qsnd.size(); ++t)
-      if (qsnd[t] == c->part) { m = (int)t; break; }
-    CHECK_ARG(m >= 0, "exchanger mismatch: a receiver lists a sender that does not send to it");
-    CHECK_ARG(cnt == qo[m + 1] - qo[m], "exchanger mismatch: segment lengths differ (SequentialBackend.jl:187)");
+    if (peer_segment(Q, dir, c->part, cnt, &m)) return -1;
     const int qdev = Q->ctx->device;
     if (qdev != c->device) {
       int can = 0;
@@ -978,7 +972,9 @@ int build_pull(int i, int n, pa_xchg* const xg[], const LocalSet& L, int dtype, 
     const int32_t b = base_id(sender_buf(Q));
     for (int64_t t = 0; t < cnt; ++t) { bid[orcv[k] + t] = b; elem[orcv[k] + t] = qo[m] + t; }
   }
-  if (dev_upload(&P.d_bid, bid) || dev_upload(&P.d_elem, elem) || dev_upload(&P.d_bases, bases)) return -1;
+  HIPC(P.d_bid.upload(bid));
+  HIPC(P.d_elem.upload(elem));
+  HIPC(P.d_bases.upload(bases));
   P.ok = true;
   return 0;
 }
@@ -993,34 +989,28 @@ int build_direct(int i, int n, pa_xchg* const xg[], const LocalSet& L) {
   std::vector<const void*> key(n);
   for (int j = 0; j < n; ++j) key[j] = (const void*)(uintptr_t)xg[j]->id;
   if (P.built && P.key == key) return 0;
-  dev_free(P.d_bid);
-  dev_free(P.d_elem);
-  dev_free(P.d_bases);
+  HIPC(hipSetDevice(X->ctx->device));
   P = pa_pull{};
   P.built = true;
   P.key = key;
-  const int64_t nslots = X->n_rcv_data;
-  std::vector<int32_t> bid(nslots);
-  std::vector<int64_t> elem(nslots);
-  for (size_t k = 0; k < X->parts_rcv.size(); ++k) {
-    const int j = L.find(X->parts_rcv[k]);
+  const XchgSide& r = X->rcv;
+  std::vector<int32_t> bid(r.n);
+  std::vector<int64_t> elem(r.n);
+  for (size_t k = 0; k < r.parts.size(); ++k) {
+    const int j = L.find(r.parts[k]);
     if (j < 0) return 0;
     const pa_xchg* Q = xg[j];
-    if ((int64_t)Q->h_lids_snd.size() != Q->n_snd_data) return 0;
+    if ((int64_t)Q->h_lids_snd.size() != Q->snd.n) return 0;
+    const int64_t cnt = r.ptrs[k + 1] - r.ptrs[k];
     int m = -1;
-    for (size_t t = 0; t < Q->parts_snd.size(); ++t)
-      if (Q->parts_snd[t] == X->ctx->part) { m = (int)t; break; }
-    CHECK_ARG(m >= 0, "exchanger mismatch: a receiver lists a sender that does not send to it");
-    const int64_t cnt = X->ptrs_rcv[k + 1] - X->ptrs_rcv[k];
-    CHECK_ARG(cnt == Q->ptrs_snd[m + 1] - Q->ptrs_snd[m],
-              "exchanger mismatch: segment lengths differ (SequentialBackend.jl:187)");
+    if (peer_segment(Q, 0, X->ctx->part, cnt, &m)) return -1;
     for (int64_t t = 0; t < cnt; ++t) {
-      bid[X->ptrs_rcv[k] + t] = j;
-      elem[X->ptrs_rcv[k] + t] = Q->h_lids_snd[Q->ptrs_snd[m] + t];
+      bid[r.ptrs[k] + t] = j;
+      elem[r.ptrs[k] + t] = Q->h_lids_snd[Q->snd.ptrs[m] + t];
     }
   }
-  HIPC(hipSetDevice(X->ctx->device));
-  if (dev_upload(&P.d_bid, bid) || dev_upload(&P.d_elem, elem)) return -1;
+  HIPC(P.d_bid.upload(bid));
+  HIPC(P.d_elem.upload(elem));
   P.ok = true;
   return 0;
 }
@@ -1080,16 +1070,6 @@ int rccl_group(std::vector<P2P>& ops) {
   return 0;
 }
 
-// Halo transport for n local parts.  dir 0 (forward): send A-layout buffers
-// (ptrs_snd) to parts_snd, receive B-layout (ptrs_rcv) from parts_rcv;
-// dir 1 (reverse): the opposite.  Each part's s_comm first waits for the
-// packs of every sender it reads from (ev_packed), then ev_recvd is recorded
-// on it.  Senders in other processes: RCCL into the receive buffer.
-// Senders in this process: when every part's pull table is usable and the
-// target vectors v are given, s_comm runs one pull-unpack kernel per part
-// that combines (op) the values straight from the senders' buffers into
-// v[i] (*unpacked = true; the caller must not unpack again); otherwise
-// device-to-device copies into the receive buffer.
 // The transport of one call, planned once (pull tables, RCCL or not), then
 // issued per part: transport_part(i) is what part i's streams get (the
 // waits for its senders' packs, the pull or the staging copies, ev_recvd),
@@ -1118,9 +1098,16 @@ int transport_plan(int n, pa_xchg* const xg[], int dtype, int dir, int op, pa_ve
   T->remote = false;
   for (int i = 0; i < n; ++i) {
     const pa_xchg* X = xg[i];
-    for (const auto* lst : {&X->parts_rcv, &X->parts_snd})
-      for (int32_t q : *lst)
-        if (T->L.find(q) < 0) T->remote = true;
+    for (int32_t q : X->into(dir).parts)
+      if (T->L.find(q) < 0) T->remote = true;
+    for (int32_t q : X->from(dir).parts) {
+      const int j = T->L.find(q);
+      int m = -1;
+      if (j < 0) T->remote = true;
+      else if (peer_segment(xg[j], 1 - dir, X->ctx->part, -1, &m))  // a segment nobody receives would be lost silently
+        PA_FAIL(std::string("exchange!: exchanger mismatch (a part in ") + side_name(dir) +
+                " does not list this part in " + side_name(1 - dir) + ")");
+    }
   }
   return 0;
 }
@@ -1131,8 +1118,7 @@ int transport_wait(int i, pa_xchg* const xg[], const TransportPlan& T) {
   pa_ctx* c = X->ctx;
   HIPC(hipSetDevice(c->device));
   HIPC(hipStreamWaitEvent(c->s_comm, c->ev_packed, 0));
-  const auto& prcv = T.dir == 0 ? X->parts_rcv : X->parts_snd;
-  for (int32_t q : prcv) {
+  for (int32_t q : X->into(T.dir).parts) {
     const int j = T.L.find(q);
     if (j >= 0 && xg[j]->ctx->ev_packed != c->ev_packed) HIPC(hipStreamWaitEvent(c->s_comm, xg[j]->ctx->ev_packed, 0));
   }
@@ -1154,34 +1140,23 @@ int transport_local(int i, pa_xchg* const xg[], pa_vec* const v[], const Transpo
     // the pull's completion is ev_recvd (recorded with the launch)
     hipEvent_t ev = c->ev_recvd;
     hipStream_t st = T.on_main ? c->s_main : c->s_comm;
-    if (dir == 0)
-      launch_pull(T.dtype, X->n_rcv_data, X->d_lids_rcv, X->plan_fwd, T.op, bid, elem, (const void* const*)bases,
-                  v[i]->d, st, ev);
-    else
-      launch_pull(T.dtype, X->n_snd_data, X->d_lids_snd, X->plan_rev, T.op, bid, elem, (const void* const*)bases,
-                  v[i]->d, st, ev);
+    const XchgSide& r = X->into(dir);
+    launch_pull(T.dtype, r.n, r.lids, r.plan, T.op, bid, elem, (const void* const*)bases, v[i]->d, st, ev);
     return 0;
   } else {
     // staging copies: receiver r, segment k from sender q (local), which
     // holds the matching segment at the position of r in its send list
-    const auto& prcv = dir == 0 ? X->parts_rcv : X->parts_snd;
-    const auto& orcv = dir == 0 ? X->ptrs_rcv : X->ptrs_snd;
-    char* brcv = (char*)(dir == 0 ? X->d_buf_rcv : X->d_buf_snd);
-    for (size_t k = 0; k < prcv.size(); ++k) {
-      const int j = T.L.find(prcv[k]);
+    const XchgSide& r = X->into(dir);
+    for (size_t k = 0; k < r.parts.size(); ++k) {
+      const int j = T.L.find(r.parts[k]);
       if (j < 0) continue;
-      pa_xchg* Q = xg[j];
-      const auto& qsnd = dir == 0 ? Q->parts_snd : Q->parts_rcv;
-      const auto& qo = dir == 0 ? Q->ptrs_snd : Q->ptrs_rcv;
-      const char* bq = (const char*)(dir == 0 ? Q->d_buf_snd : Q->d_buf_rcv);
+      const XchgSide& q = xg[j]->from(dir);
+      const int64_t cnt = r.ptrs[k + 1] - r.ptrs[k];
       int m = -1;
-      for (size_t t = 0; t < qsnd.size(); ++t)
-        if (qsnd[t] == c->part) { m = (int)t; break; }
-      CHECK_ARG(m >= 0, "exchanger mismatch: a receiver lists a sender that does not send to it");
-      const int64_t cnt = orcv[k + 1] - orcv[k];
-      CHECK_ARG(cnt == qo[m + 1] - qo[m], "exchanger mismatch: segment lengths differ (SequentialBackend.jl:187)");
+      if (peer_segment(xg[j], dir, c->part, cnt, &m)) return -1;
       if (cnt > 0)
-        HIPC(hipMemcpyAsync(brcv + orcv[k] * S, bq + qo[m] * S, (size_t)cnt * S, hipMemcpyDefault, c->s_comm));
+        HIPC(hipMemcpyAsync((char*)r.buf.p + r.ptrs[k] * S, (const char*)q.buf.p + q.ptrs[m] * S, (size_t)cnt * S,
+                            hipMemcpyDefault, c->s_comm));
     }
   }
   HIPC(hipEventRecord(c->ev_recvd, c->s_comm));
@@ -1200,12 +1175,12 @@ int transport_remote(int n, pa_xchg* const xg[], const TransportPlan& T) {
     pa_xchg* X = xg[i];
     pa_ctx* c = X->ctx;
     ncclComm_t comm = (ncclComm_t)c->comm;
-    const auto& psnd = dir == 0 ? X->parts_snd : X->parts_rcv;
-    const auto& osnd = dir == 0 ? X->ptrs_snd : X->ptrs_rcv;
-    char* bsnd = (char*)(dir == 0 ? X->d_buf_snd : X->d_buf_rcv);
-    const auto& prcv = dir == 0 ? X->parts_rcv : X->parts_snd;
-    const auto& orcv = dir == 0 ? X->ptrs_rcv : X->ptrs_snd;
-    char* brcv = (char*)(dir == 0 ? X->d_buf_rcv : X->d_buf_snd);
+    const auto& psnd = X->from(dir).parts;
+    const auto& osnd = X->from(dir).ptrs;
+    char* bsnd = (char*)X->from(dir).buf.p;
+    const auto& prcv = X->into(dir).parts;
+    const auto& orcv = X->into(dir).ptrs;
+    char* brcv = (char*)X->into(dir).buf.p;
     for (size_t k = 0; k < psnd.size(); ++k) {
       const size_t cnt = (size_t)(osnd[k + 1] - osnd[k]) * S;
       // an empty segment: the peer's matching one is empty too (SequentialBackend.jl:187)
@@ -1257,18 +1232,17 @@ int check_lids(const pa_xchg* X, const pa_vec* v) {
   return 0;
 }
 
-// Before packing into the send buffers again, wait for the copies that read
-// them in the previous exchange (local receivers record ev_recvd after their
-// copies; for RCCL sends the part's own ev_recvd covers them).
-// before part i packs into its send buffer: the previous exchange's reads
-// of it (its own unpack and its receivers' pulls) are done
+// Before part i packs into its send buffer again, its s_main waits for the
+// previous exchange's reads of it: its own unpack and its local receivers'
+// pulls or copies (they record ev_recvd after them; for RCCL sends the
+// part's own ev_recvd covers them).
 int pre_pack_wait_part(int i, pa_xchg* const xg[], const LocalSet& L) {
   xg[i]->fast_key = 0;  // the next barrier call of these exchangers waits too (spmv_impl)
   pa_ctx* c = xg[i]->ctx;
   HIPC(hipSetDevice(c->device));
   HIPC(hipStreamWaitEvent(c->s_main, c->ev_recvd, 0));
   std::vector<hipEvent_t> seen{c->ev_recvd};
-  for (const auto* lst : {&xg[i]->parts_snd, &xg[i]->parts_rcv})
+  for (const auto* lst : {&xg[i]->snd.parts, &xg[i]->rcv.parts})
     for (int32_t q : *lst) {
       const int j = L.find(q);
       if (j < 0 || j == i) continue;
@@ -2012,7 +1986,7 @@ int pa_index_create(pa_ctx* c, int64_t nlids, int64_t noids, const int32_t* oid_
             "index set: noids + nhids must equal nlids");
   CHECK_ARG(nlids < (int64_t)INT32_MAX, "index set larger than Int32 lids");
   HIPC(hipSetDevice(c->device));
-  pa_index* I = new pa_index();
+  auto I = std::make_unique<pa_index>();
   I->ctx = c;
   I->nlids = nlids;
   I->noids = noids;
@@ -2022,31 +1996,27 @@ int pa_index_create(pa_ctx* c, int64_t nlids, int64_t noids, const int32_t* oid_
   I->h_lid_to_ohid.assign(nlids, 0);
   for (int64_t i = 0; i < noids; ++i) {
     const int32_t l = oid_to_lid[i];
-    if (l < 1 || l > nlids || I->h_lid_to_ohid[l - 1] != 0) { delete I; PA_FAIL("index set: invalid or repeated oid_to_lid entry"); }
+    CHECK_ARG(l >= 1 && l <= nlids && I->h_lid_to_ohid[l - 1] == 0, "index set: invalid or repeated oid_to_lid entry");
     I->h_oid_to_lid[i] = l - 1;
     I->h_lid_to_ohid[l - 1] = (int32_t)(i + 1);
     if (l - 1 != i) I->own_contig = false;
   }
   for (int64_t i = 0; i < nhids; ++i) {
     const int32_t l = hid_to_lid[i];
-    if (l < 1 || l > nlids || I->h_lid_to_ohid[l - 1] != 0) { delete I; PA_FAIL("index set: invalid or repeated hid_to_lid entry"); }
+    CHECK_ARG(l >= 1 && l <= nlids && I->h_lid_to_ohid[l - 1] == 0, "index set: invalid or repeated hid_to_lid entry");
     I->h_hid_to_lid[i] = l - 1;
     I->h_lid_to_ohid[l - 1] = (int32_t)(-(i + 1));
     if (l - 1 != noids + i) I->ghost_contig = false;
   }
-  if (!I->own_contig && dev_upload(&I->d_oid_to_lid, I->h_oid_to_lid)) { delete I; return -1; }
-  if (!I->ghost_contig && dev_upload(&I->d_hid_to_lid, I->h_hid_to_lid)) { delete I; return -1; }
-  *out = I;
+  if (!I->own_contig) HIPC(I->d_oid_to_lid.upload(I->h_oid_to_lid));
+  if (!I->ghost_contig) HIPC(I->d_hid_to_lid.upload(I->h_hid_to_lid));
+  *out = I.release();
   return 0;
 }
 
 int pa_index_destroy(pa_index* I) {
   if (!I) return 0;
   (void)hipSetDevice(I->ctx->device);
-  dev_free(I->d_oid_to_lid);
-  dev_free(I->d_hid_to_lid);
-  dev_free(I->d_sgid);
-  dev_free(I->d_slid);
   delete I;
   return 0;
 }
@@ -2057,18 +2027,14 @@ int pa_index_set_gids(pa_index* I, const int64_t* lid_to_gid) {
   CHECK_ARG(I && (lid_to_gid || I->nlids == 0), "null argument");
   pa_ctx* c = I->ctx;
   HIPC(hipSetDevice(c->device));
-  dev_free(I->d_sgid);
-  dev_free(I->d_slid);
-  I->d_sgid = nullptr;
-  I->d_slid = nullptr;
-  int64_t* d = nullptr;
+  I->d_sgid.reset();
+  I->d_slid.reset();
   if (I->nlids > 0) {
     std::vector<int64_t> h(lid_to_gid, lid_to_gid + I->nlids);
     for (int64_t g : h) CHECK_ARG(g >= 1, "lid_to_gid: gids are 1-based");
-    if (dev_upload(&d, h)) return -1;
-    const int rc = gid_table(I->nlids, d, &I->d_sgid, &I->d_slid, c->s_main);
-    dev_free(d);
-    CHECK_ARG(rc == 0, "pa_index_set_gids: device sort failed");
+    DevBuf<int64_t> d;
+    HIPC(d.upload(h));
+    CHECK_ARG(gid_table(I->nlids, d, I->d_sgid, I->d_slid, c->s_main) == 0, "pa_index_set_gids: device sort failed");
   }
   I->has_gids = true;
   return 0;
@@ -2085,22 +2051,17 @@ int pa_add_gids(pa_index* I, int64_t n, const int64_t* gids, int64_t cap, int64_
   HIPC(hipSetDevice(c->device));
   *n_new = 0;
   if (n == 0) return 0;
-  int64_t* d = nullptr;
-  HIPC(hipMalloc((void**)&d, n * 8));
-  hipError_t e = hipMemcpy(d, gids, n * 8, hipMemcpyHostToDevice);
-  if (e != hipSuccess) { dev_free(d); HIPC(e); }
-  int64_t* out = nullptr;
+  DevBuf<int64_t> d, out;
+  HIPC(d.alloc(n));
+  HIPC(hipMemcpy(d, gids, n * 8, hipMemcpyHostToDevice));
   int64_t m = 0;
-  const int rc = gids_first_touch(n, d, I->d_sgid, I->d_slid, I->nlids, &out, &m, c->s_main);
-  dev_free(d);
-  CHECK_ARG(rc == 0, "pa_add_gids: device pass failed");
+  CHECK_ARG(gids_first_touch(n, d, I->d_sgid, I->d_slid, I->nlids, out, &m, c->s_main) == 0,
+            "pa_add_gids: device pass failed");
   *n_new = m;
-  if (m > cap || (m > 0 && !new_gids)) { dev_free(out); PA_FAIL("pa_add_gids: new_gids buffer too small (see *n_new)"); }
+  CHECK_ARG(m <= cap && (m == 0 || new_gids), "pa_add_gids: new_gids buffer too small (see *n_new)");
   if (m > 0) {
-    e = hipStreamSynchronize(c->s_main);  // (hipMemcpy runs on the null stream)
-    if (e == hipSuccess) e = hipMemcpy(new_gids, out, m * 8, hipMemcpyDeviceToHost);
-    dev_free(out);
-    HIPC(e);
+    HIPC(hipStreamSynchronize(c->s_main));  // (hipMemcpy runs on the null stream)
+    HIPC(hipMemcpy(new_gids, out, m * 8, hipMemcpyDeviceToHost));
   }
   return 0;
 }
@@ -2111,16 +2072,14 @@ int pa_index_to_lids(pa_index* I, int64_t n, int64_t* ids) {
   pa_ctx* c = I->ctx;
   HIPC(hipSetDevice(c->device));
   if (n == 0) return 0;
-  int64_t* d = nullptr;
-  HIPC(hipMalloc((void**)&d, n * 8));
-  hipError_t e = hipMemcpy(d, ids, n * 8, hipMemcpyHostToDevice);
-  const int rc = e == hipSuccess ? gids_to_lids(n, d, I->d_sgid, I->d_slid, I->nlids, c->s_main) : -1;
-  if (rc == 0) e = hipStreamSynchronize(c->s_main);  // (hipMemcpy runs on the null stream)
-  if (rc == 0 && e == hipSuccess) e = hipMemcpy(ids, d, n * 8, hipMemcpyDeviceToHost);
-  dev_free(d);
-  HIPC(e);
+  DevBuf<int64_t> d;
+  HIPC(d.alloc(n));
+  HIPC(hipMemcpy(d, ids, n * 8, hipMemcpyHostToDevice));
+  const int rc = gids_to_lids(n, d, I->d_sgid, I->d_slid, I->nlids, c->s_main);
   CHECK_ARG(rc >= 0, "pa_index_to_lids: device pass failed");
   CHECK_ARG(rc == 0, "to_lids!: a global id is not a local id of the part (KeyError)");
+  HIPC(hipStreamSynchronize(c->s_main));  // (hipMemcpy runs on the null stream)
+  HIPC(hipMemcpy(ids, d, n * 8, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -2131,11 +2090,14 @@ int pa_xchg_create(pa_ctx* c, int32_t n_rcv, const int32_t* parts_rcv, const int
   CHECK_ARG(c && out, "null argument");
   CHECK_ARG(n_rcv >= 0 && n_snd >= 0, "negative neighbour count");
   HIPC(hipSetDevice(c->device));
-  pa_xchg* X = new pa_xchg();
+  auto X = std::make_unique<pa_xchg>();
   X->ctx = c;
   X->id = g_xchg_next_id++;
-  auto take = [&](int32_t n, const int32_t* parts, const int32_t* ptrs, const int32_t* lids,
-                  std::vector<int32_t>& P, std::vector<int64_t>& O, std::vector<int32_t>& Lh) -> int {
+  // one neighbour list, checked and 0-based; Lh: its lids
+  auto take = [&](int32_t n, const int32_t* parts, const int32_t* ptrs, const int32_t* lids, XchgSide& sd,
+                  std::vector<int32_t>& Lh) -> int {
+    std::vector<int32_t>& P = sd.parts;
+    std::vector<int64_t>& O = sd.ptrs;
     P.assign(parts, parts + n);
     O.resize(n + 1);
     for (int32_t i = 0; i <= n; ++i) O[i] = (int64_t)(n == 0 && i == 0 ? 1 : ptrs[i]) - 1;
@@ -2152,39 +2114,25 @@ int pa_xchg_create(pa_ctx* c, int32_t n_rcv, const int32_t* parts_rcv, const int
     return 0;
   };
   std::vector<int32_t> hr, hs;
-  if (take(n_rcv, parts_rcv, ptrs_rcv, lids_rcv, X->parts_rcv, X->ptrs_rcv, hr) ||
-      take(n_snd, parts_snd, ptrs_snd, lids_snd, X->parts_snd, X->ptrs_snd, hs)) {
-    delete X;
+  if (take(n_rcv, parts_rcv, ptrs_rcv, lids_rcv, X->rcv, hr) || take(n_snd, parts_snd, ptrs_snd, lids_snd, X->snd, hs))
     return -1;
-  }
   for (int32_t l : hr) X->max_lid = std::max<int64_t>(X->max_lid, l);
   for (int32_t l : hs) X->max_lid = std::max<int64_t>(X->max_lid, l);
-  X->n_rcv_data = (int64_t)hr.size();
-  X->n_snd_data = (int64_t)hs.size();
-  if (dev_upload(&X->d_lids_rcv, hr) || dev_upload(&X->d_lids_snd, hs)) { delete X; return -1; }
+  X->rcv.n = (int64_t)hr.size();
+  X->snd.n = (int64_t)hs.size();
+  HIPC(X->rcv.lids.upload(hr));
+  HIPC(X->snd.lids.upload(hs));
   X->h_lids_snd = hs;
-  if (X->n_rcv_data) HIPC(hipMalloc(&X->d_buf_rcv, X->n_rcv_data * 16));
-  if (X->n_snd_data) HIPC(hipMalloc(&X->d_buf_snd, X->n_snd_data * 16));
-  if (build_plan(hr, &X->plan_fwd) || build_plan(hs, &X->plan_rev)) { delete X; return -1; }
-  *out = X;
+  if (X->rcv.n) HIPC(X->rcv.buf.alloc(X->rcv.n * 16));
+  if (X->snd.n) HIPC(X->snd.buf.alloc(X->snd.n * 16));
+  if (build_plan(hr, &X->rcv.plan) || build_plan(hs, &X->snd.plan)) return -1;
+  *out = X.release();
   return 0;
 }
 
 int pa_xchg_destroy(pa_xchg* X) {
   if (!X) return 0;
   (void)hipSetDevice(X->ctx->device);
-  dev_free(X->d_lids_rcv);
-  dev_free(X->d_lids_snd);
-  dev_free(X->d_buf_rcv);
-  dev_free(X->d_buf_snd);
-  dev_free(X->d_buf_snd2);
-  free_plan(X->plan_fwd);
-  free_plan(X->plan_rev);
-  for (pa_pull* t : {&X->pull[0], &X->pull[1], &X->direct, &X->pull_alt}) {
-    dev_free(t->d_bid);
-    dev_free(t->d_elem);
-    dev_free(t->d_bases);
-  }
   delete X;
   return 0;
 }
@@ -2195,7 +2143,7 @@ int pa_vec_create(pa_ctx* c, int dtype, int64_t n, pa_vec** out) {
   CHECK_ARG(valid_dtype(dtype), "invalid dtype");
   CHECK_ARG(n >= 0, "negative length");
   HIPC(hipSetDevice(c->device));
-  pa_vec* v = new pa_vec();
+  auto v = std::make_unique<pa_vec>();
   v->ctx = c;
   v->dtype = dtype;
   v->n = n;
@@ -2203,12 +2151,12 @@ int pa_vec_create(pa_ctx* c, int dtype, int64_t n, pa_vec** out) {
     // kVecPad bytes on both sides: the SpMV's 16 B x runs may start up to
     // 3 elements before lid 0 or end up to 3 after the last lid
     const size_t bytes = (size_t)n * dtype_size(dtype) + 2 * kVecPad;
-    hipError_t e = hipMalloc(&v->base, bytes);
-    if (e != hipSuccess) { delete v; PA_FAIL(std::string("hipMalloc(vector) failed: ") + hipGetErrorString(e)); }
-    v->d = (char*)v->base + kVecPad;
+    const hipError_t e = v->base.alloc(bytes);
+    if (e != hipSuccess) PA_FAIL(std::string("hipMalloc(vector) failed: ") + hipGetErrorString(e));
+    v->d = (char*)v->base.p + kVecPad;
     HIPC(hipMemsetAsync(v->base, 0, bytes, c->s_main));
   }
-  *out = v;
+  *out = v.release();
   return 0;
 }
 
@@ -2216,7 +2164,6 @@ int pa_vec_destroy(pa_vec* v) {
   if (!v) return 0;
   (void)hipSetDevice(v->ctx->device);
   (void)hipStreamSynchronize(v->ctx->s_main);
-  dev_free(v->base);
   delete v;
   return 0;
 }
@@ -2553,8 +2500,8 @@ int pa_mat_from_dcoo(const pa_coo* coo, int ids_global, int64_t nrows_lids, int6
                      const pa_index* cols, int64_t* csc_nnz, int64_t* colptr_out, int64_t* rowval_out, pa_mat** out) {
   CHECK_ARG(coo, "null argument");
   CHECK_ARG(rows && rows->ctx == coo->ctx && cols && cols->ctx == coo->ctx, "COO and index sets of different parts");
-  return mat_from_coo_impl(coo->ctx, coo->dtype, 8, ids_global, nrows_lids, ncols_lids, coo->n, coo->d_I, coo->d_J,
-                           coo->d_V, hipMemcpyDeviceToDevice, rows, cols, -1, csc_nnz, colptr_out, rowval_out, out);
+  return mat_from_coo_impl(coo->ctx, coo->dtype, 8, ids_global, nrows_lids, ncols_lids, coo->l.n, coo->l.I, coo->l.J,
+                           coo->l.V, hipMemcpyDeviceToDevice, rows, cols, -1, csc_nnz, colptr_out, rowval_out, out);
 }
 
 int pa_mat_from_coo_csr(pa_ctx* c, int dtype, int index_bytes, int ids_global, int Bi, int64_t nrows_lids,
@@ -2572,8 +2519,8 @@ int pa_mat_from_dcoo_csr(const pa_coo* coo, int ids_global, int Bi, int64_t nrow
   CHECK_ARG(coo, "null argument");
   CHECK_ARG(Bi == 0 || Bi == 1, "Bi (index base) must be 0 or 1");
   CHECK_ARG(rows && rows->ctx == coo->ctx && cols && cols->ctx == coo->ctx, "COO and index sets of different parts");
-  return mat_from_coo_impl(coo->ctx, coo->dtype, 8, ids_global, nrows_lids, ncols_lids, coo->n, coo->d_I, coo->d_J,
-                           coo->d_V, hipMemcpyDeviceToDevice, rows, cols, Bi, nnz, rowptr_out, colval_out, out);
+  return mat_from_coo_impl(coo->ctx, coo->dtype, 8, ids_global, nrows_lids, ncols_lids, coo->l.n, coo->l.I, coo->l.J,
+                           coo->l.V, hipMemcpyDeviceToDevice, rows, cols, Bi, nnz, rowptr_out, colval_out, out);
 }
 
 }  // extern "C"
@@ -2603,7 +2550,6 @@ int mat_from_coo_impl(pa_ctx* c, int dtype, int index_bytes, int ids_global, int
   hipStream_t st = c->s_main;
   const size_t S = dtype_size(dtype);
   SetupTrace tr(st);
-  // the arrays coo_compress and coo_row_order allocate are adopted as they return
   DevBuf<void> dI, dJ, dV, cval;
   DevBuf<int32_t> crow, ccol, rl2o, cl2o, slen_d, sghost_d, lidx_d, lcol_d;
   DevBuf<int64_t> dcolptr, idx2, rowptr, gflag, grank, lptr_d, nzs;
@@ -2627,12 +2573,8 @@ int mat_from_coo_impl(pa_ctx* c, int dtype, int index_bytes, int ids_global, int
   int64_t nu = 0;
   hipError_t e = hipSuccess;
   {
-    int32_t *pr = nullptr, *pc = nullptr;
-    void* pv = nullptr;
-    int64_t* pp = nullptr;
-    const int rc = coo_compress(dtype, index_bytes, nrows_lids, ncols_lids, ncoo, dI, dJ, dV, csr ? 1 : 0, &nu, &pr, &pc,
-                                &pv, &pp, st, &e);
-    crow.adopt(pr), ccol.adopt(pc), cval.adopt(pv), dcolptr.adopt(pp);
+    const int rc = coo_compress(dtype, index_bytes, nrows_lids, ncols_lids, ncoo, dI, dJ, dV, csr ? 1 : 0, &nu, crow, ccol,
+                                cval, dcolptr, st, &e);
     if (rc < 0) HIPC(e);
     CHECK_ARG(rc == 0, "sparse: COO index out of range (BoundsError)");
   }
@@ -2660,16 +2602,9 @@ int mat_from_coo_impl(pa_ctx* c, int dtype, int index_bytes, int ids_global, int
   A->csc_nnz = nu;
   const int64_t nrows = A->main.nrows;
   int64_t nnz = 0, ngh = 0;
-  {
-    uint64_t* pk = nullptr;
-    int64_t *pi = nullptr, *pr = nullptr, *pf = nullptr, *pg = nullptr;
-    int32_t *pl = nullptr, *ps = nullptr;
-    const int rc = coo_row_order(nu, crow, ccol, rl2o, cl2o, nrows, cols->noids, ncols_lids, A->H, &pk, &pi, &pr, &pf,
-                                 &pg, &pl, &ps, &nnz, &ngh, st, &e);
-    key2.adopt(pk), idx2.adopt(pi), rowptr.adopt(pr), gflag.adopt(pf), grank.adopt(pg), slen_d.adopt(pl),
-        sghost_d.adopt(ps);
-    if (rc) HIPC(e);
-  }
+  if (coo_row_order(nu, crow, ccol, rl2o, cl2o, nrows, cols->noids, ncols_lids, A->H, key2, idx2, rowptr, gflag, grank,
+                    slen_d, sghost_d, &nnz, &ngh, st, &e))
+    HIPC(e);
   tr.mark("row order");
   A->nnz = nnz;
   const int64_t ns = (nrows + A->H - 1) / A->H;
@@ -2740,41 +2675,42 @@ int mat_from_coo_impl(pa_ctx* c, int dtype, int index_bytes, int ids_global, int
 // counts it receives (in the order of its receiving neighbour list); the new
 // lists.
 struct CooSide {
-  int64_t *sI = nullptr, *sJ = nullptr;
-  void* sV = nullptr;
+  CooList s;  // the triplets it sends
   std::vector<int64_t> cnt, off, rcnt, roff;
-  int64_t *nI = nullptr, *nJ = nullptr;
-  void* nV = nullptr;
-  int64_t nn = 0;
+  CooList nw;                // its new list
+  DevBuf<int64_t> dsc, drc;  // the counts it sends / receives over RCCL
+};
+// The sides of a call's parts.  The parts may sit on several devices: what a
+// side still holds is released with its part's device current.
+struct CooSides {
+  std::vector<CooSide> sd;
+  pa_coo* const* coo;
+  CooSides(int n, pa_coo* const coo[]) : sd(n), coo(coo) {}
+  ~CooSides() {
+    for (size_t i = 0; i < sd.size(); ++i) {
+      (void)hipSetDevice(coo[i]->ctx->device);
+      sd[i] = CooSide{};
+    }
+  }
+  CooSide& operator[](int i) { return sd[i]; }
 };
 
-void coo_free_sides(int n, pa_coo* const coo[], std::vector<CooSide>& sd) {
-  for (int i = 0; i < n; ++i) {
-    (void)hipSetDevice(coo[i]->ctx->device);
-    for (void* p : {(void*)sd[i].sI, (void*)sd[i].sJ, sd[i].sV, (void*)sd[i].nI, (void*)sd[i].nJ, sd[i].nV})
-      if (p) (void)hipFree(p);
-    sd[i] = CooSide{};
-  }
-}
-
-// sd[i].sI/sJ/sV/cnt hold part i's packed segments.  to_ghosts = false
-// (assemble!): a part sends to its parts_rcv and receives from its
-// parts_snd; to_ghosts = true (exchange!): it sends to its parts_snd and
-// receives from its parts_rcv.  Delivery is the reference's
+// sd[i].s/cnt hold part i's packed segments.  dir 1 (assemble!): a part
+// sends to its parts_rcv and receives from its parts_snd; dir 0 (exchange!):
+// it sends to its parts_snd and receives from its parts_rcv — the vector
+// transport's directions, so the sending list is from(dir) and the receiving
+// one into(dir).  Delivery is the reference's
 // (SequentialBackend.jl:167-200 / MPIBackend.jl:261-309): the sender's
 // segment for q lands in q's slot of the sender.  Counts go first, then I,
 // J, V per segment: device / peer copies between the parts of this process,
 // one RCCL group for the others.  Every part ends with its own triplets
-// followed by the received segments in the order of its receiving list; sd
-// is freed on return.
-int coo_move_segments(const char* who, int n, pa_coo* const coo[], pa_xchg* const xg[], std::vector<CooSide>& sd,
-                      bool to_ghosts) {
+// followed by the received segments in the order of its receiving list.
+int coo_move_segments(const std::string& who, int n, pa_coo* const coo[], pa_xchg* const xg[], CooSides& sd, int dir) {
   const size_t S = dtype_size(coo[0]->dtype);
-  auto to_list = [&](const pa_xchg* X) -> const std::vector<int32_t>& { return to_ghosts ? X->parts_snd : X->parts_rcv; };
-  auto from_list = [&](const pa_xchg* X) -> const std::vector<int32_t>& { return to_ghosts ? X->parts_rcv : X->parts_snd; };
-  const char* to_name = to_ghosts ? "parts_snd" : "parts_rcv";
-  const char* from_name = to_ghosts ? "parts_rcv" : "parts_snd";
-  auto free_all = [&]() { coo_free_sides(n, coo, sd); };
+  auto mismatch = [&](const char* listed, const char* missing) {
+    set_error(who + ": exchanger mismatch (a part in " + listed + " does not list this part in " + missing + ")");
+    return -1;
+  };
   for (int i = 0; i < n; ++i) {
     sd[i].off.assign(sd[i].cnt.size() + 1, 0);
     for (size_t k = 0; k < sd[i].cnt.size(); ++k) sd[i].off[k + 1] = sd[i].off[k] + sd[i].cnt[k];
@@ -2784,91 +2720,74 @@ int coo_move_segments(const char* who, int n, pa_coo* const coo[], pa_xchg* cons
   bool remote = false;
   for (int i = 0; i < n; ++i) {
     pa_xchg* X = xg[i];
-    const auto& from = from_list(X);
+    const auto& from = X->into(dir).parts;
     sd[i].rcnt.assign(from.size(), 0);
     for (size_t j = 0; j < from.size(); ++j) {
       const int jj = L.find(from[j]);
+      int k = -1;
       if (jj < 0) { remote = true; continue; }
-      const auto& q = to_list(xg[jj]);
-      const auto it = std::find(q.begin(), q.end(), X->ctx->part);
-      if (it == q.end()) {
-        free_all();
-        PA_FAIL(std::string(who) + ": exchanger mismatch (a part in " + from_name + " does not list this part in " +
-                to_name + ")");
-      }
-      sd[i].rcnt[j] = sd[jj].cnt[it - q.begin()];
+      if (peer_segment(xg[jj], dir, X->ctx->part, -1, &k)) return mismatch(side_name(1 - dir), side_name(dir));
+      sd[i].rcnt[j] = sd[jj].cnt[k];
     }
-    for (int32_t q : to_list(X)) {
+    for (int32_t q : X->from(dir).parts) {
       const int jj = L.find(q);
+      int k = -1;
       if (jj < 0) { remote = true; continue; }
-      const auto& back = from_list(xg[jj]);  // a segment nobody receives would be lost silently
-      if (std::find(back.begin(), back.end(), X->ctx->part) == back.end()) {
-        free_all();
-        PA_FAIL(std::string(who) + ": exchanger mismatch (a part in " + to_name + " does not list this part in " +
-                from_name + ")");
-      }
+      // a segment nobody receives would be lost silently
+      if (peer_segment(xg[jj], 1 - dir, X->ctx->part, -1, &k)) return mismatch(side_name(dir), side_name(1 - dir));
     }
   }
   if (remote) {  // counts of the other processes' parts: one RCCL group of 8 B messages
-    std::vector<int64_t*> dsc(n, nullptr), drc(n, nullptr);
-    auto free_cnt = [&]() {
-      for (int i = 0; i < n; ++i) { (void)hipSetDevice(coo[i]->ctx->device); dev_free(dsc[i]); dev_free(drc[i]); }
-    };
     std::vector<P2P> ops;
     for (int i = 0; i < n; ++i) {
       pa_xchg* X = xg[i];
       pa_ctx* c = X->ctx;
-      const auto &to = to_list(X), &from = from_list(X);
-      if (!c->comm) {
-        free_cnt();
-        free_all();
-        PA_FAIL(std::string(who) + ": a neighbour is not held by this process and no RCCL communicator was initialised");
-      }
+      CooSide& d = sd[i];
+      const auto &to = X->from(dir).parts, &from = X->into(dir).parts;
+      CHECK_ARG(c->comm, who + ": a neighbour is not held by this process and no RCCL communicator was initialised");
       HIPC(hipSetDevice(c->device));
-      if (dev_upload(&dsc[i], sd[i].cnt)) { free_cnt(); free_all(); return -1; }
-      if (!from.empty()) HIPC(hipMalloc((void**)&drc[i], from.size() * 8));
+      HIPC(d.dsc.upload(d.cnt));
+      if (!from.empty()) HIPC(d.drc.alloc(from.size()));
       for (size_t k = 0; k < to.size(); ++k)
         if (L.find(to[k]) < 0)
-          ops.push_back({c->part, to[k], true, (char*)(dsc[i] + k), 8, c->peer_rank(to[k]), (ncclComm_t)c->comm,
+          ops.push_back({c->part, to[k], true, (char*)(d.dsc.p + k), 8, c->peer_rank(to[k]), (ncclComm_t)c->comm,
                          c->s_main});
       for (size_t j = 0; j < from.size(); ++j)
         if (L.find(from[j]) < 0)
-          ops.push_back({from[j], c->part, false, (char*)(drc[i] + j), 8, c->peer_rank(from[j]), (ncclComm_t)c->comm,
+          ops.push_back({from[j], c->part, false, (char*)(d.drc.p + j), 8, c->peer_rank(from[j]), (ncclComm_t)c->comm,
                          c->s_main});
     }
-    if (rccl_group(ops)) { free_cnt(); free_all(); return -1; }
+    if (rccl_group(ops)) return -1;
     for (int i = 0; i < n; ++i) {
       pa_xchg* X = xg[i];
-      const auto& from = from_list(X);
+      const auto& from = X->into(dir).parts;
       HIPC(hipSetDevice(X->ctx->device));
       HIPC(hipStreamSynchronize(X->ctx->s_main));
       std::vector<int64_t> got(from.size());
-      if (!got.empty()) HIPC(hipMemcpy(got.data(), drc[i], got.size() * 8, hipMemcpyDeviceToHost));
+      if (!got.empty()) HIPC(hipMemcpy(got.data(), sd[i].drc, got.size() * 8, hipMemcpyDeviceToHost));
       for (size_t j = 0; j < from.size(); ++j)
         if (L.find(from[j]) < 0) sd[i].rcnt[j] = got[j];
     }
-    free_cnt();
   }
   // 3. the new lists: the local triplets, then the received segments in the
   // order of the receiving list (Interfaces.jl:2470-2486, 2570-2586)
   for (int i = 0; i < n; ++i) {
-    pa_coo* C = coo[i];
+    const CooList& own = coo[i]->l;
     CooSide& d = sd[i];
     d.roff.assign(d.rcnt.size() + 1, 0);
     for (size_t j = 0; j < d.rcnt.size(); ++j) d.roff[j + 1] = d.roff[j] + d.rcnt[j];
-    d.nn = C->n + d.roff.back();
-    HIPC(hipSetDevice(C->ctx->device));
-    if (d.nn > 0) {
-      hipError_t e = hipMalloc((void**)&d.nI, d.nn * 8);
-      if (e == hipSuccess) e = hipMalloc((void**)&d.nJ, d.nn * 8);
-      if (e == hipSuccess) e = hipMalloc(&d.nV, d.nn * S);
-      if (e != hipSuccess) { free_all(); HIPC(e); }
+    d.nw.n = own.n + d.roff.back();
+    HIPC(hipSetDevice(coo[i]->ctx->device));
+    if (d.nw.n > 0) {
+      HIPC(d.nw.I.alloc(d.nw.n));
+      HIPC(d.nw.J.alloc(d.nw.n));
+      HIPC(d.nw.V.alloc(d.nw.n * S));
     }
-    if (C->n > 0) {
-      hipStream_t st = C->ctx->s_main;
-      HIPC(hipMemcpyAsync(d.nI, C->d_I, C->n * 8, hipMemcpyDeviceToDevice, st));
-      HIPC(hipMemcpyAsync(d.nJ, C->d_J, C->n * 8, hipMemcpyDeviceToDevice, st));
-      HIPC(hipMemcpyAsync(d.nV, C->d_V, C->n * S, hipMemcpyDeviceToDevice, st));
+    if (own.n > 0) {
+      hipStream_t st = coo[i]->ctx->s_main;
+      HIPC(hipMemcpyAsync(d.nw.I, own.I, own.n * 8, hipMemcpyDeviceToDevice, st));
+      HIPC(hipMemcpyAsync(d.nw.J, own.J, own.n * 8, hipMemcpyDeviceToDevice, st));
+      HIPC(hipMemcpyAsync(d.nw.V, own.V, own.n * S, hipMemcpyDeviceToDevice, st));
     }
   }
   for (int i = 0; i < n; ++i) {  // every pack has finished before any part reads it
@@ -2882,36 +2801,37 @@ int coo_move_segments(const char* who, int n, pa_coo* const coo[], pa_xchg* cons
     pa_xchg* X = xg[i];
     pa_ctx* c = X->ctx;
     CooSide& d = sd[i];
-    const auto &to = to_list(X), &from = from_list(X);
+    int64_t *nI = d.nw.I, *nJ = d.nw.J;
+    char* nV = (char*)d.nw.V.p;
+    const auto &to = X->from(dir).parts, &from = X->into(dir).parts;
     HIPC(hipSetDevice(c->device));
     for (size_t j = 0; j < from.size(); ++j) {
       const int64_t m = d.rcnt[j];
       if (m == 0) continue;
-      const int64_t at = coo[i]->n + d.roff[j];
+      const int64_t at = coo[i]->l.n + d.roff[j];
       const int jj = L.find(from[j]);
       if (jj < 0) {
         const int q = from[j], pr = c->peer_rank(q);
         ncclComm_t cm = (ncclComm_t)c->comm;
-        ops.push_back({q, c->part, false, (char*)(d.nI + at), (size_t)m * 8, pr, cm, c->s_main});
-        ops.push_back({q, c->part, false, (char*)(d.nJ + at), (size_t)m * 8, pr, cm, c->s_main});
-        ops.push_back({q, c->part, false, (char*)d.nV + at * S, (size_t)m * S, pr, cm, c->s_main});
+        ops.push_back({q, c->part, false, (char*)(nI + at), (size_t)m * 8, pr, cm, c->s_main});
+        ops.push_back({q, c->part, false, (char*)(nJ + at), (size_t)m * 8, pr, cm, c->s_main});
+        ops.push_back({q, c->part, false, nV + at * S, (size_t)m * S, pr, cm, c->s_main});
         continue;
       }
-      const auto& qt = to_list(xg[jj]);
-      const int64_t k = std::find(qt.begin(), qt.end(), c->part) - qt.begin();
-      const CooSide& src = sd[jj];
-      const int64_t from_at = src.off[k];
+      int k = -1;
+      if (peer_segment(xg[jj], dir, c->part, -1, &k)) return -1;  // (checked in step 2)
+      const CooList& src = sd[jj].s;
+      const int64_t from_at = sd[jj].off[k];
+      const char* sV = (const char*)src.V.p;
       const int sdev = xg[jj]->ctx->device;
       if (sdev == c->device) {
-        HIPC(hipMemcpyAsync(d.nI + at, src.sI + from_at, m * 8, hipMemcpyDeviceToDevice, c->s_main));
-        HIPC(hipMemcpyAsync(d.nJ + at, src.sJ + from_at, m * 8, hipMemcpyDeviceToDevice, c->s_main));
-        HIPC(hipMemcpyAsync((char*)d.nV + at * S, (const char*)src.sV + from_at * S, m * S, hipMemcpyDeviceToDevice,
-                            c->s_main));
+        HIPC(hipMemcpyAsync(nI + at, src.I.p + from_at, m * 8, hipMemcpyDeviceToDevice, c->s_main));
+        HIPC(hipMemcpyAsync(nJ + at, src.J.p + from_at, m * 8, hipMemcpyDeviceToDevice, c->s_main));
+        HIPC(hipMemcpyAsync(nV + at * S, sV + from_at * S, m * S, hipMemcpyDeviceToDevice, c->s_main));
       } else {
-        HIPC(hipMemcpyPeerAsync(d.nI + at, c->device, src.sI + from_at, sdev, m * 8, c->s_main));
-        HIPC(hipMemcpyPeerAsync(d.nJ + at, c->device, src.sJ + from_at, sdev, m * 8, c->s_main));
-        HIPC(hipMemcpyPeerAsync((char*)d.nV + at * S, c->device, (const char*)src.sV + from_at * S, sdev, m * S,
-                                c->s_main));
+        HIPC(hipMemcpyPeerAsync(nI + at, c->device, src.I.p + from_at, sdev, m * 8, c->s_main));
+        HIPC(hipMemcpyPeerAsync(nJ + at, c->device, src.J.p + from_at, sdev, m * 8, c->s_main));
+        HIPC(hipMemcpyPeerAsync(nV + at * S, c->device, sV + from_at * S, sdev, m * S, c->s_main));
       }
     }
     for (size_t k = 0; k < to.size(); ++k) {
@@ -2920,33 +2840,21 @@ int coo_move_segments(const char* who, int n, pa_coo* const coo[], pa_xchg* cons
       if (m == 0 || L.find(q) >= 0) continue;
       const int pr = c->peer_rank(q);
       ncclComm_t cm = (ncclComm_t)c->comm;
-      ops.push_back({c->part, q, true, (char*)(d.sI + d.off[k]), (size_t)m * 8, pr, cm, c->s_main});
-      ops.push_back({c->part, q, true, (char*)(d.sJ + d.off[k]), (size_t)m * 8, pr, cm, c->s_main});
-      ops.push_back({c->part, q, true, (char*)d.sV + d.off[k] * S, (size_t)m * S, pr, cm, c->s_main});
+      ops.push_back({c->part, q, true, (char*)(d.s.I.p + d.off[k]), (size_t)m * 8, pr, cm, c->s_main});
+      ops.push_back({c->part, q, true, (char*)(d.s.J.p + d.off[k]), (size_t)m * 8, pr, cm, c->s_main});
+      ops.push_back({c->part, q, true, (char*)d.s.V.p + d.off[k] * S, (size_t)m * S, pr, cm, c->s_main});
     }
   }
-  if (!ops.empty() && rccl_group(ops)) { free_all(); return -1; }
+  if (!ops.empty() && rccl_group(ops)) return -1;
   for (int i = 0; i < n; ++i) {
     HIPC(hipSetDevice(coo[i]->ctx->device));
     HIPC(hipStreamSynchronize(coo[i]->ctx->s_main));
   }
   // 5. swap in the new lists
   for (int i = 0; i < n; ++i) {
-    pa_coo* C = coo[i];
-    CooSide& d = sd[i];
-    HIPC(hipSetDevice(C->ctx->device));
-    dev_free(C->d_I);
-    dev_free(C->d_J);
-    dev_free(C->d_V);
-    C->d_I = d.nI;
-    C->d_J = d.nJ;
-    C->d_V = d.nV;
-    C->n = d.nn;
-    d.nI = nullptr;
-    d.nJ = nullptr;
-    d.nV = nullptr;
+    HIPC(hipSetDevice(coo[i]->ctx->device));
+    coo[i]->l = std::move(sd[i].nw);
   }
-  free_all();
   return 0;
 }
 
@@ -2955,6 +2863,7 @@ int coo_move_segments(const char* who, int n, pa_coo* const coo[], pa_xchg* cons
 // to the ghost holders) over the n parts of this process
 int coo_send_all(bool to_ghosts, int n, pa_coo* const coo[], const pa_index* const rows[], pa_xchg* const xg[]) {
   const std::string who = to_ghosts ? "exchange!" : "assemble!";
+  const int dir = to_ghosts ? 0 : 1;  // the triplets travel as the vector values of that call do
   CHECK_ARG(n >= 1 && coo && rows && xg && coo[0], "null argument");
   const int dt = coo[0]->dtype;
   for (int i = 0; i < n; ++i) {
@@ -2965,30 +2874,21 @@ int coo_send_all(bool to_ghosts, int n, pa_coo* const coo[], const pa_index* con
     CHECK_ARG(xg[i]->max_lid < rows[i]->nlids, who + ": the exchanger's lids exceed rows' local ids");
   }
   TuneScope ts(coo[0]->ctx);
-  std::vector<CooSide> sd(n);
+  CooSides sd(n, coo);
   // 1. assemble!: group the triplets of rows owned elsewhere by owner, zero
   // them locally; exchange!: group the triplets of rows held elsewhere as
   // ghosts by (last) holder, zero the unsent ghost rows' values
   for (int i = 0; i < n; ++i) {
     pa_coo* C = coo[i];
-    pa_xchg* X = xg[i];
     const pa_index* R = rows[i];
     HIPC(hipSetDevice(C->ctx->device));
-    const int rc =
-        to_ghosts ? coo_exchange_pack(dt, C->n, C->d_I, C->d_J, C->d_V, R->d_sgid, R->d_slid, R->nlids,
-                                      R->h_lid_to_ohid, (int)X->parts_snd.size(), X->d_lids_snd, X->ptrs_snd,
-                                      &sd[i].sI, &sd[i].sJ, &sd[i].sV, &sd[i].cnt, C->ctx->s_main)
-                  : coo_assemble_pack(dt, C->n, C->d_I, C->d_J, C->d_V, R->d_sgid, R->d_slid, R->nlids,
-                                      R->h_lid_to_ohid, (int)X->parts_rcv.size(), X->d_lids_rcv, X->ptrs_rcv,
-                                      &sd[i].sI, &sd[i].sJ, &sd[i].sV, &sd[i].cnt, C->ctx->s_main);
-    if (rc) {
-      coo_free_sides(n, coo, sd);
-      if (rc < 0) PA_FAIL(who + "(I,J,V,rows): device pass failed");
-      if (rc == 2) PA_FAIL("assemble!(I,J,V,rows): a ghost row's owner is not in the exchanger's parts_rcv (KeyError)");
-      PA_FAIL("to_lids!: a row global id is not a local id of rows (KeyError)");
-    }
+    const int rc = coo_send_pack(to_ghosts, dt, C->l, R->d_sgid, R->d_slid, R->nlids, R->h_lid_to_ohid, xg[i]->from(dir),
+                                 &sd[i].s, &sd[i].cnt, C->ctx->s_main);
+    if (rc < 0) PA_FAIL(who + "(I,J,V,rows): device pass failed");
+    if (rc == 2) PA_FAIL("assemble!(I,J,V,rows): a ghost row's owner is not in the exchanger's parts_rcv (KeyError)");
+    if (rc) PA_FAIL("to_lids!: a row global id is not a local id of rows (KeyError)");
   }
-  return coo_move_segments(who.c_str(), n, coo, xg, sd, to_ghosts);
+  return coo_move_segments(who, n, coo, xg, sd, dir);
 }
 }  // namespace
 
@@ -3006,19 +2906,15 @@ int pa_coo_create(pa_ctx* c, int dtype, int64_t n, const int64_t* I, const int64
   auto C = std::make_unique<pa_coo>();
   C->ctx = c;
   C->dtype = dtype;
-  C->n = n;
+  C->l.n = n;
   if (n > 0) {
     const size_t S = dtype_size(dtype);
-    hipError_t e = hipMalloc((void**)&C->d_I, n * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&C->d_J, n * 8);
-    if (e == hipSuccess) e = hipMalloc(&C->d_V, n * S);
-    if (e == hipSuccess) e = hipMemcpy(C->d_I, I, n * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(C->d_J, J, n * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(C->d_V, V, n * S, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-      pa_coo_destroy(C.release());
-      HIPC(e);
-    }
+    HIPC(C->l.I.alloc(n));
+    HIPC(C->l.J.alloc(n));
+    HIPC(C->l.V.alloc(n * S));
+    HIPC(hipMemcpy(C->l.I, I, n * 8, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(C->l.J, J, n * 8, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(C->l.V, V, n * S, hipMemcpyHostToDevice));
   }
   *out = C.release();
   return 0;
@@ -3028,27 +2924,25 @@ int pa_coo_destroy(pa_coo* C) {
   if (!C) return 0;
   (void)hipSetDevice(C->ctx->device);
   (void)hipStreamSynchronize(C->ctx->s_main);
-  dev_free(C->d_I);
-  dev_free(C->d_J);
-  dev_free(C->d_V);
   delete C;
   return 0;
 }
 
 int pa_coo_size(const pa_coo* C, int64_t* n) {
   CHECK_ARG(C && n, "null argument");
-  *n = C->n;
+  *n = C->l.n;
   return 0;
 }
 
 int pa_coo_download(const pa_coo* C, int64_t* I, int64_t* J, void* V) {
-  CHECK_ARG(C && (C->n == 0 || (I && J && V)), "null argument");
-  if (C->n == 0) return 0;
+  CHECK_ARG(C && (C->l.n == 0 || (I && J && V)), "null argument");
+  const int64_t n = C->l.n;
+  if (n == 0) return 0;
   HIPC(hipSetDevice(C->ctx->device));
   HIPC(hipStreamSynchronize(C->ctx->s_main));
-  HIPC(hipMemcpy(I, C->d_I, C->n * 8, hipMemcpyDeviceToHost));
-  HIPC(hipMemcpy(J, C->d_J, C->n * 8, hipMemcpyDeviceToHost));
-  HIPC(hipMemcpy(V, C->d_V, C->n * dtype_size(C->dtype), hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(I, C->l.I, n * 8, hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(J, C->l.J, n * 8, hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(V, C->l.V, n * dtype_size(C->dtype), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -3188,8 +3082,8 @@ int pa_mat_exchange_all(int n, pa_mat* const A[], pa_xchg* const xg[], int op, i
     HIPC(hipSetDevice(c->device));
     if (zero_sent) {
       unsigned char z[16] = {0};
-      if (reverse) launch_fill(A[i]->dtype, xg[i]->n_rcv_data, 0, xg[i]->d_lids_rcv, A[i]->main.val, z, c->s_main);
-      else launch_fill(A[i]->dtype, xg[i]->n_snd_data, 0, xg[i]->d_lids_snd, A[i]->main.val, z, c->s_main);
+      const XchgSide& sent = xg[i]->from(reverse ? 1 : 0);
+      launch_fill(A[i]->dtype, sent.n, 0, sent.lids, A[i]->main.val, z, c->s_main);
     }
     if (refresh_side(A[i], c->s_main)) return -1;
   }
@@ -3448,11 +3342,11 @@ static int group_ok(int n, pa_mat* const A[], pa_xchg* const xg[], bool any_x, i
   if (!knobs().halo_pull) return 0;
   LocalSet L = local_set(n, xg);
   for (int i = 0; i < n; ++i)
-    for (const auto* lst : {&xg[i]->parts_snd, &xg[i]->parts_rcv})
+    for (const auto* lst : {&xg[i]->snd.parts, &xg[i]->rcv.parts})
       for (int32_t q : *lst)
         if (L.find(q) < 0) return 0;
   for (int i = 0; i < n; ++i)
-    if (!xg[i]->plan_fwd.unique) return 0;
+    if (!xg[i]->rcv.plan.unique) return 0;
   if (knobs().halo_direct) {
     bool ok = true;
     for (int i = 0; i < n && ok; ++i) {
@@ -3504,8 +3398,8 @@ static int spmv_grouped(const SpmvCall& C, bool direct) {
       for (int i = i0; i < n && i < i0 + PA_GROUP_MAX; ++i) {
         pa_xchg* X = xg[i];
         const int k = qg.np++;
-        qg.n[k] = X->n_rcv_data;
-        qg.lids[k] = X->d_lids_rcv;
+        qg.n[k] = X->rcv.n;
+        qg.lids[k] = X->rcv.lids;
         qg.bid[k] = X->direct.d_bid;
         qg.elem[k] = X->direct.d_elem;
         qg.bases[k] = (const void* const*)bases;
@@ -3524,10 +3418,10 @@ static int spmv_grouped(const SpmvCall& C, bool direct) {
       for (int i = i0; i < n && i < i0 + PA_GROUP_MAX; ++i) {
         pa_xchg* X = xg[i];
         const int k = pg.np++;
-        pg.n[k] = X->n_snd_data;
-        pg.lids[k] = X->d_lids_snd;
+        pg.n[k] = X->snd.n;
+        pg.lids[k] = X->snd.lids;
         pg.v[k] = x[i]->d;
-        pg.buf[k] = X->d_buf_snd;
+        pg.buf[k] = X->snd.buf;
       }
       launch_pack_group(dt, pg, sm);
     }
@@ -3539,8 +3433,8 @@ static int spmv_grouped(const SpmvCall& C, bool direct) {
         pa_xchg* X = xg[i];
         const pa_pull& P = X->pull[0];
         const int k = qg.np++;
-        qg.n[k] = X->n_rcv_data;
-        qg.lids[k] = X->d_lids_rcv;
+        qg.n[k] = X->rcv.n;
+        qg.lids[k] = X->rcv.lids;
         qg.bid[k] = P.d_bid;
         qg.elem[k] = P.d_elem;
         qg.bases[k] = (const void* const*)P.d_bases;
@@ -3680,7 +3574,7 @@ static int launch_phase(const SpmvCall& C, SlicePhase phase, int i, hipStream_t 
 //      (halo_barrier 2: s_main waits ev_barrier and pulls itself, after its
 //      interior slices, then the boundary slices: one runtime call less per
 //      part, the pull no longer beside the interior).
-// b alternates between d_buf_snd and d_buf_snd2 from one call to the next,
+// b alternates between snd.buf and buf_snd2 from one call to the next,
 // so a pack does not wait for the readers of the previous call's buffer: the
 // last reads of b before pack(k+2) are the pulls of call k, and every part
 // issued its pack(k+1) after its boundary(k), i.e. after its pull(k); pack(k+2)
@@ -3706,9 +3600,9 @@ static int spmv_barrier_issue(const SpmvCall& C, const TransportPlan& T, bool th
   TB.on_main = pull_on_main;
   if (TB.alt) {  // the second send buffers and the pull tables reading them
     for (int i = 0; i < n; ++i)
-      if (!xg[i]->d_buf_snd2 && xg[i]->n_snd_data) {
+      if (!xg[i]->buf_snd2 && xg[i]->snd.n) {
         HIPC(hipSetDevice(xg[i]->ctx->device));
-        HIPC(hipMalloc(&xg[i]->d_buf_snd2, xg[i]->n_snd_data * 16));
+        HIPC(xg[i]->buf_snd2.alloc(xg[i]->snd.n * 16));
       }
     for (int i = 0; i < n; ++i) {
       if (build_pull(i, n, xg, T.L, dt, 0, true)) return -1;
@@ -3726,7 +3620,7 @@ static int spmv_barrier_issue(const SpmvCall& C, const TransportPlan& T, bool th
     pa_ctx* c = X->ctx;
     if (!chain && pre_pack_wait_part(i, xg, L)) return -1;
     HIPC(hipSetDevice(c->device));
-    launch_pack(dt, X->n_snd_data, X->d_lids_snd, x[i]->d, TB.alt ? X->d_buf_snd2 : X->d_buf_snd, c->s_main,
+    launch_pack(dt, X->snd.n, X->snd.lids, x[i]->d, TB.alt ? X->buf_snd2 : X->snd.buf, c->s_main,
                 c->ev_packed);
     // the barrier stream's wait for this pack, from this part's thread (the
     // record of ev_barrier follows once every part's job is done)
@@ -3836,7 +3730,7 @@ static int spmv_impl(int n, pa_mat* const A[], pa_vec* const y[], const pa_index
   auto pack = [&](int i) -> int {
     pa_ctx* c = xg[i]->ctx;
     HIPC(hipSetDevice(c->device));
-    launch_pack(dt, xg[i]->n_snd_data, xg[i]->d_lids_snd, x[i]->d, xg[i]->d_buf_snd, c->s_main);
+    launch_pack(dt, xg[i]->snd.n, xg[i]->snd.lids, x[i]->d, xg[i]->snd.buf, c->s_main);
     HIPC(hipEventRecord(c->ev_packed, c->s_main));
     return 0;
   };
@@ -3855,8 +3749,8 @@ static int spmv_impl(int n, pa_mat* const A[], pa_vec* const y[], const pa_index
     if (any_x) {
       if (!pulled_on_main) HIPC(hipStreamWaitEvent(c->s_main, c->ev_recvd, 0));
       if (!pulled)
-        launch_unpack(dt, xg[i]->n_rcv_data, xg[i]->d_lids_rcv, xg[i]->plan_fwd, PA_REPLACE,
-                      xg[i]->d_buf_rcv, x[i]->d, c->s_main);
+        launch_unpack(dt, xg[i]->rcv.n, xg[i]->rcv.lids, xg[i]->rcv.plan, PA_REPLACE,
+                      xg[i]->rcv.buf, x[i]->d, c->s_main);
     }
     if (C.tslot[i]) HIPC(hipEventRecord(C.tslot[i][2], c->s_main));
     // slices reading ghosts and the side rows (after the halo)
@@ -3942,31 +3836,24 @@ int pa_exchange_all(int n, pa_vec* const v[], pa_xchg* const xg[], const pa_inde
     CHECK_ARG(v[i]->ctx == xg[i]->ctx, "exchange!: vector and exchanger of different parts");
     if (check_lids(xg[i], v[i])) return -1;
   }
+  const int dir = reverse ? 1 : 0;
   if (pre_pack_wait(n, xg)) return -1;
   for (int i = 0; i < n; ++i) {
-    pa_xchg* X = xg[i];
-    pa_ctx* c = X->ctx;
+    pa_ctx* c = xg[i]->ctx;
+    const XchgSide& s = xg[i]->from(dir);
     HIPC(hipSetDevice(c->device));
-    if (!reverse)
-      launch_pack(dt, X->n_snd_data, X->d_lids_snd, v[i]->d, X->d_buf_snd, c->s_main);
-    else
-      launch_pack(dt, X->n_rcv_data, X->d_lids_rcv, v[i]->d, X->d_buf_rcv, c->s_main);
+    launch_pack(dt, s.n, s.lids, v[i]->d, s.buf, c->s_main);
     HIPC(hipEventRecord(c->ev_packed, c->s_main));
   }
   HIPC(hipGetLastError());
   bool pulled = false;
-  if (transport(n, xg, dt, reverse ? 1 : 0, op, v, &pulled)) return -1;
+  if (transport(n, xg, dt, dir, op, v, &pulled)) return -1;
   for (int i = 0; i < n; ++i) {
-    pa_xchg* X = xg[i];
-    pa_ctx* c = X->ctx;
+    pa_ctx* c = xg[i]->ctx;
+    const XchgSide& r = xg[i]->into(dir);
     HIPC(hipSetDevice(c->device));
     HIPC(hipStreamWaitEvent(c->s_main, c->ev_recvd, 0));
-    if (pulled) {
-    } else if (!reverse) {
-      launch_unpack(dt, X->n_rcv_data, X->d_lids_rcv, X->plan_fwd, op, X->d_buf_rcv, v[i]->d, c->s_main);
-    } else {
-      launch_unpack(dt, X->n_snd_data, X->d_lids_snd, X->plan_rev, op, X->d_buf_snd, v[i]->d, c->s_main);
-    }
+    if (!pulled) launch_unpack(dt, r.n, r.lids, r.plan, op, r.buf, v[i]->d, c->s_main);
     if (zero_ghosts) {
       CHECK_ARG(idx && idx[i] && idx[i]->nlids == v[i]->n, "assemble!: index set of the vector required");
       unsigned char z[16] = {0};

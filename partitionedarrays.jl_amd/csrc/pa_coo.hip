@@ -202,48 +202,45 @@ inline int bits_for(uint64_t maxkey) {
 }
 
 // stable sort of (key, idx) pairs in place (double buffer + temp storage)
-hipError_t sort_pairs(uint64_t*& key, int64_t*& idx, int64_t n, int end_bit, hipStream_t st) {
+hipError_t sort_pairs(DevBuf<uint64_t>& key, DevBuf<int64_t>& idx, int64_t n, int end_bit, hipStream_t st) {
   if (n <= 1) return hipSuccess;
-  uint64_t* k2 = nullptr;
-  int64_t* i2 = nullptr;
-  void* tmp = nullptr;
+  DevBuf<uint64_t> k2;
+  DevBuf<int64_t> i2;
+  DevBuf<void> tmp;
   size_t tb = 0;
-  hipError_t e = hipMalloc((void**)&k2, n * 8);
-  if (e == hipSuccess) e = hipMalloc((void**)&i2, n * 8);
-  rocprim::double_buffer<uint64_t> kb(key, k2);
-  rocprim::double_buffer<int64_t> ib(idx, i2);
+  hipError_t e = k2.alloc(n);
+  if (e == hipSuccess) e = i2.alloc(n);
+  rocprim::double_buffer<uint64_t> kb(key.p, k2.p);
+  rocprim::double_buffer<int64_t> ib(idx.p, i2.p);
   if (e == hipSuccess) e = rocprim::radix_sort_pairs(nullptr, tb, kb, ib, (size_t)n, 0, (unsigned)end_bit, st);
-  if (e == hipSuccess) e = hipMalloc(&tmp, tb ? tb : 1);
-  if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp, tb, kb, ib, (size_t)n, 0, (unsigned)end_bit, st);
+  if (e == hipSuccess) e = tmp.alloc(tb ? tb : 1);
+  if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp.p, tb, kb, ib, (size_t)n, 0, (unsigned)end_bit, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (tmp) (void)hipFree(tmp);
   // keep the buffers holding the result
-  if (kb.current() != key) { (void)hipFree(key); key = kb.current(); } else (void)hipFree(k2);
-  if (ib.current() != idx) { (void)hipFree(idx); idx = ib.current(); } else (void)hipFree(i2);
+  if (kb.current() != key.p) std::swap(key.p, k2.p);
+  if (ib.current() != idx.p) std::swap(idx.p, i2.p);
   return e;
 }
 
 hipError_t inclusive_sum(const int64_t* in, int64_t* out, int64_t n, hipStream_t st) {
   if (n <= 0) return hipSuccess;
   size_t tb = 0;
-  void* tmp = nullptr;
+  DevBuf<void> tmp;
   hipError_t e = rocprim::inclusive_scan(nullptr, tb, in, out, (size_t)n, rocprim::plus<int64_t>(), st);
-  if (e == hipSuccess) e = hipMalloc(&tmp, tb ? tb : 1);
-  if (e == hipSuccess) e = rocprim::inclusive_scan(tmp, tb, in, out, (size_t)n, rocprim::plus<int64_t>(), st);
+  if (e == hipSuccess) e = tmp.alloc(tb ? tb : 1);
+  if (e == hipSuccess) e = rocprim::inclusive_scan(tmp.p, tb, in, out, (size_t)n, rocprim::plus<int64_t>(), st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (tmp) (void)hipFree(tmp);
   return e;
 }
 
 hipError_t exclusive_sum(const int64_t* in, int64_t* out, int64_t n, hipStream_t st) {
   if (n <= 0) return hipSuccess;
   size_t tb = 0;
-  void* tmp = nullptr;
+  DevBuf<void> tmp;
   hipError_t e = rocprim::exclusive_scan(nullptr, tb, in, out, (int64_t)0, (size_t)n, rocprim::plus<int64_t>(), st);
-  if (e == hipSuccess) e = hipMalloc(&tmp, tb ? tb : 1);
-  if (e == hipSuccess) e = rocprim::exclusive_scan(tmp, tb, in, out, (int64_t)0, (size_t)n, rocprim::plus<int64_t>(), st);
+  if (e == hipSuccess) e = tmp.alloc(tb ? tb : 1);
+  if (e == hipSuccess) e = rocprim::exclusive_scan(tmp.p, tb, in, out, (int64_t)0, (size_t)n, rocprim::plus<int64_t>(), st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (tmp) (void)hipFree(tmp);
   return e;
 }
 
@@ -257,131 +254,107 @@ void seg_sum_t(int64_t nu, int64_t n, const int64_t* start, const uint64_t* key,
 
 }  // namespace
 
-#define PA_HIP_TRY(expr)                     \
-  do {                                       \
-    hipError_t e_ = (expr);                  \
-    if (e_ != hipSuccess) {                  \
-      err = e_;                              \
-      goto done;                             \
-    }                                        \
+// leave the function with `ret` when a HIP call fails (the DevBuf locals
+// and the caller's outputs release what was allocated so far)
+#define PA_HIP_OR(expr, ret)             \
+  do {                                   \
+    if ((expr) != hipSuccess) return ret; \
   } while (0)
 
 // Phase A: sparse(I, J, V, m, n, +) → CSC on the device (0-based rows/cols,
 // values combined).  I, J: 1-based device arrays (index_bytes 4 or 8).
-// On success the caller owns *crow, *ccol, *cval (nu entries) and *colptr
-// (ncols+1, 0-based offsets).  Returns 1 on an out-of-range index.
+// Outputs: crow, ccol, cval (nu entries) and colptr (ncols+1, 0-based
+// offsets).  Returns 1 on an out-of-range index, -1 on a HIP error (*err).
 // csr: sparsecsr instead — the nonzeros in row-major (CSR) order and
-// *colptr the row pointers (m+1).
+// colptr the row pointers (m+1).
 int coo_compress(int dtype, int index_bytes, int64_t m, int64_t ncols, int64_t n, const void* dI, const void* dJ,
-                 const void* dV, int csr, int64_t* nu_out, int32_t** crow, int32_t** ccol, void** cval,
-                 int64_t** colptr, hipStream_t st, hipError_t* err_out) {
-  hipError_t err = hipSuccess;
+                 const void* dV, int csr, int64_t* nu_out, DevBuf<int32_t>& crow, DevBuf<int32_t>& ccol,
+                 DevBuf<void>& cval, DevBuf<int64_t>& colptr, hipStream_t st, hipError_t* err) {
   const size_t S = dtype_size(dtype);
-  uint64_t* key = nullptr;
-  int64_t *idx = nullptr, *head = nullptr, *segid = nullptr, *start = nullptr;
-  int* bad = nullptr;
+  DevBuf<uint64_t> key;
+  DevBuf<int64_t> idx, head, segid, start;
+  DevBuf<int> bad;
   int hbad = 0;
   int64_t nu = 0;
-  *crow = nullptr;
-  *ccol = nullptr;
-  *cval = nullptr;
-  *colptr = nullptr;
-  int rc = 0;
+  *nu_out = 0;
+  *err = hipSuccess;
   const int64_t nptr = csr ? m : ncols;  // columns (CSC) or rows (CSR) of the compressed axis
-  PA_HIP_TRY(hipMalloc((void**)colptr, (nptr + 1) * 8));
+  PA_HIP_OR(*err = colptr.alloc(nptr + 1), -1);
   if (n > 0) {
-    PA_HIP_TRY(hipMalloc((void**)&key, n * 8));
-    PA_HIP_TRY(hipMalloc((void**)&idx, n * 8));
-    PA_HIP_TRY(hipMalloc((void**)&bad, sizeof(int)));
-    PA_HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int), st));
+    PA_HIP_OR(*err = key.alloc(n), -1);
+    PA_HIP_OR(*err = idx.alloc(n), -1);
+    PA_HIP_OR(*err = bad.alloc(1), -1);
+    PA_HIP_OR(*err = hipMemsetAsync(bad, 0, sizeof(int), st), -1);
     if (index_bytes == 8)
       hipLaunchKernelGGL(k_coo_keys<int64_t>, grid1(n), dim3(256), 0, st, n, (const int64_t*)dI, (const int64_t*)dJ,
-                         m, ncols, csr, key, idx, bad);
+                         m, ncols, csr, key.p, idx.p, bad.p);
     else
       hipLaunchKernelGGL(k_coo_keys<int32_t>, grid1(n), dim3(256), 0, st, n, (const int32_t*)dI, (const int32_t*)dJ,
-                         m, ncols, csr, key, idx, bad);
-    PA_HIP_TRY(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, st));
-    PA_HIP_TRY(hipStreamSynchronize(st));
-    if (hbad) { rc = 1; goto done; }
-    PA_HIP_TRY(sort_pairs(key, idx, n, bits_for((uint64_t)m * (uint64_t)ncols), st));
-    PA_HIP_TRY(hipMalloc((void**)&head, n * 8));
-    PA_HIP_TRY(hipMalloc((void**)&segid, n * 8));
-    hipLaunchKernelGGL(k_heads, grid1(n), dim3(256), 0, st, n, key, head);
-    PA_HIP_TRY(inclusive_sum(head, segid, n, st));
-    PA_HIP_TRY(copy_sync(&nu, segid + n - 1, 8, hipMemcpyDeviceToHost, st));
-    PA_HIP_TRY(hipMalloc((void**)&start, nu * 8));
-    hipLaunchKernelGGL(k_seg_start, grid1(n), dim3(256), 0, st, n, head, segid, start);
-    PA_HIP_TRY(hipMalloc((void**)crow, nu * 4));
-    PA_HIP_TRY(hipMalloc((void**)ccol, nu * 4));
-    PA_HIP_TRY(hipMalloc(cval, nu * S));
+                         m, ncols, csr, key.p, idx.p, bad.p);
+    PA_HIP_OR(*err = hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, st), -1);
+    PA_HIP_OR(*err = hipStreamSynchronize(st), -1);
+    if (hbad) return 1;
+    PA_HIP_OR(*err = sort_pairs(key, idx, n, bits_for((uint64_t)m * (uint64_t)ncols), st), -1);
+    PA_HIP_OR(*err = head.alloc(n), -1);
+    PA_HIP_OR(*err = segid.alloc(n), -1);
+    hipLaunchKernelGGL(k_heads, grid1(n), dim3(256), 0, st, n, key.p, head.p);
+    PA_HIP_OR(*err = inclusive_sum(head, segid, n, st), -1);
+    PA_HIP_OR(*err = copy_sync(&nu, segid.p + n - 1, 8, hipMemcpyDeviceToHost, st), -1);
+    PA_HIP_OR(*err = start.alloc(nu), -1);
+    hipLaunchKernelGGL(k_seg_start, grid1(n), dim3(256), 0, st, n, head.p, segid.p, start.p);
+    PA_HIP_OR(*err = crow.alloc(nu), -1);
+    PA_HIP_OR(*err = ccol.alloc(nu), -1);
+    PA_HIP_OR(*err = cval.alloc(nu * S), -1);
     switch (dtype) {
-      case PA_F32: seg_sum_t<float>(nu, n, start, key, idx, dV, m, ncols, csr, *crow, *ccol, *cval, st); break;
-      case PA_F64: seg_sum_t<double>(nu, n, start, key, idx, dV, m, ncols, csr, *crow, *ccol, *cval, st); break;
-      case PA_C64: seg_sum_t<c64>(nu, n, start, key, idx, dV, m, ncols, csr, *crow, *ccol, *cval, st); break;
-      case PA_C128: seg_sum_t<c128>(nu, n, start, key, idx, dV, m, ncols, csr, *crow, *ccol, *cval, st); break;
+      case PA_F32: seg_sum_t<float>(nu, n, start, key, idx, dV, m, ncols, csr, crow, ccol, cval, st); break;
+      case PA_F64: seg_sum_t<double>(nu, n, start, key, idx, dV, m, ncols, csr, crow, ccol, cval, st); break;
+      case PA_C64: seg_sum_t<c64>(nu, n, start, key, idx, dV, m, ncols, csr, crow, ccol, cval, st); break;
+      case PA_C128: seg_sum_t<c128>(nu, n, start, key, idx, dV, m, ncols, csr, crow, ccol, cval, st); break;
     }
   }
-  hipLaunchKernelGGL(k_colptr, grid1(nptr + 1), dim3(256), 0, st, nptr, nu, csr ? *crow : *ccol, *colptr);
-  PA_HIP_TRY(hipGetLastError());
-  PA_HIP_TRY(hipStreamSynchronize(st));
-done:
-  for (void* p : {(void*)key, (void*)idx, (void*)head, (void*)segid, (void*)start, (void*)bad})
-    if (p) (void)hipFree(p);
+  hipLaunchKernelGGL(k_colptr, grid1(nptr + 1), dim3(256), 0, st, nptr, nu, csr ? crow.p : ccol.p, colptr.p);
+  PA_HIP_OR(*err = hipGetLastError(), -1);
+  PA_HIP_OR(*err = hipStreamSynchronize(st), -1);
   *nu_out = nu;
-  *err_out = err;
-  if (err != hipSuccess || rc) {
-    for (void** p : {(void**)crow, (void**)ccol, cval, (void**)colptr})
-      if (*p) { (void)hipFree(*p); *p = nullptr; }
-    return err != hipSuccess ? -1 : rc;
-  }
   return 0;
 }
 
 // Phase B, first half: order the owned rows' entries (key2/idx2, nnz owned
 // entries first), row pointers, per-slice lengths / ghost flags, ghost-row
-// flags and ranks.  Device outputs are owned by the caller.
+// flags and ranks.
 int coo_row_order(int64_t nu, const int32_t* crow, const int32_t* ccol, const int32_t* rl2o, const int32_t* cl2o,
-                  int64_t nrows, int64_t noids_c, int64_t ncols, int H, uint64_t** key2, int64_t** idx2,
-                  int64_t** rowptr, int64_t** gflag, int64_t** grank, int32_t** slen, int32_t** sghost,
-                  int64_t* nnz_out, int64_t* ngh_out, hipStream_t st, hipError_t* err_out) {
-  hipError_t err = hipSuccess;
+                  int64_t nrows, int64_t noids_c, int64_t ncols, int H, DevBuf<uint64_t>& key2, DevBuf<int64_t>& idx2,
+                  DevBuf<int64_t>& rowptr, DevBuf<int64_t>& gflag, DevBuf<int64_t>& grank, DevBuf<int32_t>& slen,
+                  DevBuf<int32_t>& sghost, int64_t* nnz_out, int64_t* ngh_out, hipStream_t st, hipError_t* err) {
   const int64_t ns = (nrows + H - 1) / H;
   int64_t nnz = 0, ngh = 0, last = 0, lastf = 0;
-  *key2 = nullptr; *idx2 = nullptr; *rowptr = nullptr; *gflag = nullptr; *grank = nullptr;
-  *slen = nullptr; *sghost = nullptr;
+  *nnz_out = *ngh_out = 0;
+  *err = hipSuccess;
   const int64_t nb = nu > 0 ? nu : 1;
-  PA_HIP_TRY(hipMalloc((void**)key2, nb * 8));
-  PA_HIP_TRY(hipMalloc((void**)idx2, nb * 8));
-  PA_HIP_TRY(hipMalloc((void**)gflag, nb * 8));
-  PA_HIP_TRY(hipMalloc((void**)grank, nb * 8));
-  PA_HIP_TRY(hipMalloc((void**)rowptr, (nrows + 1) * 8));
-  PA_HIP_TRY(hipMalloc((void**)slen, (ns > 0 ? ns : 1) * 4));
-  PA_HIP_TRY(hipMalloc((void**)sghost, (ns > 0 ? ns : 1) * 4));
+  PA_HIP_OR(*err = key2.alloc(nb), -1);
+  PA_HIP_OR(*err = idx2.alloc(nb), -1);
+  PA_HIP_OR(*err = gflag.alloc(nb), -1);
+  PA_HIP_OR(*err = grank.alloc(nb), -1);
+  PA_HIP_OR(*err = rowptr.alloc(nrows + 1), -1);
+  PA_HIP_OR(*err = slen.alloc(ns > 0 ? ns : 1), -1);
+  PA_HIP_OR(*err = sghost.alloc(ns > 0 ? ns : 1), -1);
   if (nu > 0) {
-    hipLaunchKernelGGL(k_own_keys, grid1(nu), dim3(256), 0, st, nu, crow, ccol, rl2o, cl2o, noids_c, ncols, *key2,
-                       *idx2, *gflag);
-    PA_HIP_TRY(exclusive_sum(*gflag, *grank, nu, st));
-    PA_HIP_TRY(copy_sync(&last, *grank + nu - 1, 8, hipMemcpyDeviceToHost, st));
-    PA_HIP_TRY(copy_sync(&lastf, *gflag + nu - 1, 8, hipMemcpyDeviceToHost, st));
+    hipLaunchKernelGGL(k_own_keys, grid1(nu), dim3(256), 0, st, nu, crow, ccol, rl2o, cl2o, noids_c, ncols, key2.p,
+                       idx2.p, gflag.p);
+    PA_HIP_OR(*err = exclusive_sum(gflag, grank, nu, st), -1);
+    PA_HIP_OR(*err = copy_sync(&last, grank.p + nu - 1, 8, hipMemcpyDeviceToHost, st), -1);
+    PA_HIP_OR(*err = copy_sync(&lastf, gflag.p + nu - 1, 8, hipMemcpyDeviceToHost, st), -1);
     ngh = last + lastf;
     nnz = nu - ngh;
     // ghost rows carry key2 = ~0: sort all bits of the owned range + 1
     const uint64_t maxk = (uint64_t)(nrows > 0 ? nrows : 1) * (uint64_t)ncols;
-    PA_HIP_TRY(sort_pairs(*key2, *idx2, nu, ngh ? 64 : bits_for(maxk), st));
+    PA_HIP_OR(*err = sort_pairs(key2, idx2, nu, ngh ? 64 : bits_for(maxk), st), -1);
   }
-  hipLaunchKernelGGL(k_rowptr, grid1(nrows + 1), dim3(256), 0, st, nrows, nnz, *key2, ncols, *rowptr);
-  PA_HIP_TRY(hipGetLastError());
-  PA_HIP_TRY(hipStreamSynchronize(st));
-done:
+  hipLaunchKernelGGL(k_rowptr, grid1(nrows + 1), dim3(256), 0, st, nrows, nnz, key2.p, ncols, rowptr.p);
+  PA_HIP_OR(*err = hipGetLastError(), -1);
+  PA_HIP_OR(*err = hipStreamSynchronize(st), -1);
   *nnz_out = nnz;
   *ngh_out = ngh;
-  *err_out = err;
-  if (err != hipSuccess) {
-    for (void** p : {(void**)key2, (void**)idx2, (void**)rowptr, (void**)gflag, (void**)grank, (void**)slen,
-                     (void**)sghost})
-      if (*p) { (void)hipFree(*p); *p = nullptr; }
-    return -1;
-  }
   return 0;
 }
 
@@ -483,109 +456,86 @@ __global__ void k_first_touch(int64_t m, const uint64_t* __restrict__ key, const
     }
 }
 
+// the largest of n device values (it bounds the radix passes of a gid sort)
+static hipError_t device_max(const int64_t* in, int64_t n, int64_t* out, hipStream_t st) {
+  size_t tb = 0;
+  DevBuf<void> tmp;
+  DevBuf<int64_t> dmax;
+  hipError_t e = dmax.alloc(1);
+  if (e == hipSuccess) e = rocprim::reduce(nullptr, tb, in, dmax.p, (int64_t)0, (size_t)n, rocprim::maximum<int64_t>(), st);
+  if (e == hipSuccess) e = tmp.alloc(tb ? tb : 1);
+  if (e == hipSuccess) e = rocprim::reduce(tmp.p, tb, in, dmax.p, (int64_t)0, (size_t)n, rocprim::maximum<int64_t>(), st);
+  if (e == hipSuccess) e = hipMemcpyAsync(out, dmax, 8, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  return e;
+}
+
 // sorted (gid, lid) table of lid_to_gid (device input, n lids)
-int gid_table(int64_t n, const int64_t* d_lid_to_gid, uint64_t** sgid, int64_t** slid, hipStream_t st) {
-  *sgid = nullptr;
-  *slid = nullptr;
+int gid_table(int64_t n, const int64_t* d_lid_to_gid, DevBuf<uint64_t>& sgid, DevBuf<int64_t>& slid, hipStream_t st) {
+  sgid.reset();
+  slid.reset();
   if (n <= 0) return 0;
   int64_t maxg = 0;
-  if (hipMalloc((void**)sgid, n * 8) != hipSuccess || hipMalloc((void**)slid, n * 8) != hipSuccess) return -1;
-  if (hipMemcpyAsync(*sgid, d_lid_to_gid, n * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) return -1;
-  hipLaunchKernelGGL(k_iota_i64, grid1(n), dim3(256), 0, st, n, *slid);
-  // the largest gid bounds the radix passes
-  {
-    size_t tb = 0;
-    void* tmp = nullptr;
-    int64_t* dmax = nullptr;
-    if (hipMalloc((void**)&dmax, 8) != hipSuccess) return -1;
-    hipError_t e = rocprim::reduce(nullptr, tb, d_lid_to_gid, dmax, (int64_t)0, (size_t)n, rocprim::maximum<int64_t>(), st);
-    if (e == hipSuccess) e = hipMalloc(&tmp, tb ? tb : 1);
-    if (e == hipSuccess) e = rocprim::reduce(tmp, tb, d_lid_to_gid, dmax, (int64_t)0, (size_t)n, rocprim::maximum<int64_t>(), st);
-    if (e == hipSuccess) e = hipMemcpyAsync(&maxg, dmax, 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (tmp) (void)hipFree(tmp);
-    (void)hipFree(dmax);
-    if (e != hipSuccess) return -1;
-  }
-  return sort_pairs(*sgid, *slid, n, bits_for((uint64_t)(maxg > 0 ? maxg : 1)), st) == hipSuccess ? 0 : -1;
+  PA_HIP_OR(sgid.alloc(n), -1);
+  PA_HIP_OR(slid.alloc(n), -1);
+  PA_HIP_OR(hipMemcpyAsync(sgid, d_lid_to_gid, n * 8, hipMemcpyDeviceToDevice, st), -1);
+  hipLaunchKernelGGL(k_iota_i64, grid1(n), dim3(256), 0, st, n, slid.p);
+  PA_HIP_OR(device_max(d_lid_to_gid, n, &maxg, st), -1);
+  PA_HIP_OR(sort_pairs(sgid, slid, n, bits_for((uint64_t)(maxg > 0 ? maxg : 1)), st), -1);
+  return 0;
 }
 
 // ids (n, device, 1-based gids) → 1-based lids; returns 1 if a gid is absent
 int gids_to_lids(int64_t n, int64_t* ids, const uint64_t* sgid, const int64_t* slid, int64_t nl, hipStream_t st) {
   if (n <= 0) return 0;
-  int* bad = nullptr;
+  DevBuf<int> bad;
   int hbad = 0;
-  if (hipMalloc((void**)&bad, sizeof(int)) != hipSuccess) return -1;
+  PA_HIP_OR(bad.alloc(1), -1);
   hipError_t e = hipMemsetAsync(bad, 0, sizeof(int), st);
-  hipLaunchKernelGGL(k_to_lids, grid1(n), dim3(256), 0, st, n, ids, sgid, slid, nl, bad);
+  hipLaunchKernelGGL(k_to_lids, grid1(n), dim3(256), 0, st, n, ids, sgid, slid, nl, bad.p);
   if (e == hipSuccess) e = hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  (void)hipFree(bad);
   if (e != hipSuccess) return -1;
   return hbad ? 1 : 0;
 }
 
 // add_gids!: the gids (device, n) absent from the table, each once, in order
-// of first occurrence.  *out (device, *m entries) is owned by the caller.
+// of first occurrence: out (device, *m_out entries)
 int gids_first_touch(int64_t n, const int64_t* gids, const uint64_t* sgid, const int64_t* slid, int64_t nl,
-                     int64_t** out, int64_t* m_out, hipStream_t st) {
-  *out = nullptr;
+                     DevBuf<int64_t>& out, int64_t* m_out, hipStream_t st) {
+  out.reset();
   *m_out = 0;
   if (n <= 0) return 0;
-  int64_t *flag = nullptr, *pos = nullptr, *val = nullptr, *head = nullptr, *rank = nullptr, *val2 = nullptr;
-  uint64_t *key = nullptr, *key2 = nullptr;
+  DevBuf<int64_t> flag, pos, val, head, rank, val2;
+  DevBuf<uint64_t> key, key2;
   int64_t m = 0, lastf = 0, u = 0, maxg = 0;
-  hipError_t e = hipMalloc((void**)&flag, n * 8);
-  if (e == hipSuccess) e = hipMalloc((void**)&pos, n * 8);
-  if (e != hipSuccess) goto fail;
-  hipLaunchKernelGGL(k_absent, grid1(n), dim3(256), 0, st, n, gids, sgid, slid, nl, flag);
-  e = exclusive_sum(flag, pos, n, st);
-  if (e == hipSuccess) e = copy_sync(&m, pos + n - 1, 8, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = copy_sync(&lastf, flag + n - 1, 8, hipMemcpyDeviceToHost, st);
-  if (e != hipSuccess) goto fail;
+  PA_HIP_OR(flag.alloc(n), -1);
+  PA_HIP_OR(pos.alloc(n), -1);
+  hipLaunchKernelGGL(k_absent, grid1(n), dim3(256), 0, st, n, gids, sgid, slid, nl, flag.p);
+  PA_HIP_OR(exclusive_sum(flag, pos, n, st), -1);
+  PA_HIP_OR(copy_sync(&m, pos.p + n - 1, 8, hipMemcpyDeviceToHost, st), -1);
+  PA_HIP_OR(copy_sync(&lastf, flag.p + n - 1, 8, hipMemcpyDeviceToHost, st), -1);
   m += lastf;
-  if (m > 0) {
-    e = hipMalloc((void**)&key, m * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&val, m * 8);
-    if (e != hipSuccess) goto fail;
-    hipLaunchKernelGGL(k_compact, grid1(n), dim3(256), 0, st, n, gids, flag, pos, key, val);
-    (void)hipFree(flag); flag = nullptr;
-    (void)hipFree(pos); pos = nullptr;
-    {
-      size_t tb = 0;
-      void* tmp = nullptr;
-      int64_t* dmax = nullptr;
-      e = hipMalloc((void**)&dmax, 8);
-      if (e == hipSuccess) e = rocprim::reduce(nullptr, tb, (const int64_t*)key, dmax, (int64_t)0, (size_t)m, rocprim::maximum<int64_t>(), st);
-      if (e == hipSuccess) e = hipMalloc(&tmp, tb ? tb : 1);
-      if (e == hipSuccess) e = rocprim::reduce(tmp, tb, (const int64_t*)key, dmax, (int64_t)0, (size_t)m, rocprim::maximum<int64_t>(), st);
-      if (e == hipSuccess) e = hipMemcpyAsync(&maxg, dmax, 8, hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess) e = hipStreamSynchronize(st);
-      if (tmp) (void)hipFree(tmp);
-      if (dmax) (void)hipFree(dmax);
-      if (e != hipSuccess) goto fail;
-    }
-    e = sort_pairs(key, val, m, bits_for((uint64_t)(maxg > 0 ? maxg : 1)), st);
-    if (e == hipSuccess) e = hipMalloc((void**)&head, m * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&rank, m * 8);
-    if (e != hipSuccess) goto fail;
-    hipLaunchKernelGGL(k_heads, grid1(m), dim3(256), 0, st, m, key, head);
-    e = inclusive_sum(head, rank, m, st);
-    if (e == hipSuccess) e = copy_sync(&u, rank + m - 1, 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMalloc((void**)&key2, u * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&val2, u * 8);
-    if (e != hipSuccess) goto fail;
-    hipLaunchKernelGGL(k_first_touch, grid1(m), dim3(256), 0, st, m, key, val, head, rank, key2, val2);
-    e = sort_pairs(key2, val2, u, bits_for((uint64_t)n), st);
-    if (e != hipSuccess) goto fail;
-    *out = val2;
-    val2 = nullptr;
-    *m_out = u;
-  }
-fail:
-  for (void* p : {(void*)flag, (void*)pos, (void*)val, (void*)head, (void*)rank, (void*)val2, (void*)key, (void*)key2})
-    if (p) (void)hipFree(p);
-  return e == hipSuccess ? 0 : -1;
+  if (m == 0) return 0;
+  PA_HIP_OR(key.alloc(m), -1);
+  PA_HIP_OR(val.alloc(m), -1);
+  hipLaunchKernelGGL(k_compact, grid1(n), dim3(256), 0, st, n, gids, flag.p, pos.p, key.p, val.p);
+  flag.reset();
+  pos.reset();
+  PA_HIP_OR(device_max((const int64_t*)key.p, m, &maxg, st), -1);
+  PA_HIP_OR(sort_pairs(key, val, m, bits_for((uint64_t)(maxg > 0 ? maxg : 1)), st), -1);
+  PA_HIP_OR(head.alloc(m), -1);
+  PA_HIP_OR(rank.alloc(m), -1);
+  hipLaunchKernelGGL(k_heads, grid1(m), dim3(256), 0, st, m, key.p, head.p);
+  PA_HIP_OR(inclusive_sum(head, rank, m, st), -1);
+  PA_HIP_OR(copy_sync(&u, rank.p + m - 1, 8, hipMemcpyDeviceToHost, st), -1);
+  PA_HIP_OR(key2.alloc(u), -1);
+  PA_HIP_OR(val2.alloc(u), -1);
+  hipLaunchKernelGGL(k_first_touch, grid1(m), dim3(256), 0, st, m, key.p, val.p, head.p, rank.p, key2.p, val2.p);
+  PA_HIP_OR(sort_pairs(key2, val2, u, bits_for((uint64_t)n), st), -1);
+  out = std::move(val2);
+  *m_out = u;
+  return 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -658,102 +608,43 @@ static void coo_pack_t(int64_t nr, const int64_t* idx, const int64_t* I, const i
 // The common tail of the two send sides: key[k] = 0 (stays) or 1 + segment,
 // idx[k] = k.  Sorts by key (stable: input order inside a segment), counts
 // the segments into cnt[0..nseg) and copies the sent triplets out, segment
-// after segment, into *sI, *sJ, *sV (device, owned by the caller).  key and
-// idx may be reallocated by the sort.
-static hipError_t coo_pack_by_key(int dtype, int64_t n, const int64_t* I, const int64_t* J, void* V, uint64_t*& key,
-                                  int64_t*& idx, int nseg, bool zero_src, int64_t** sI, int64_t** sJ, void** sV,
-                                  std::vector<int64_t>* cnt, hipStream_t st) {
+// after segment, into *out.
+static hipError_t coo_pack_by_key(int dtype, const CooList& in, DevBuf<uint64_t>& key, DevBuf<int64_t>& idx, int nseg,
+                                  bool zero_src, CooList* out, std::vector<int64_t>* cnt, hipStream_t st) {
   const size_t S = dtype_size(dtype);
-  int64_t* first = nullptr;
+  const int64_t n = in.n;
+  DevBuf<int64_t> first;
   std::vector<int64_t> hfirst(nseg + 2, -1);
-  int64_t nloc = n;
   hipError_t e = sort_pairs(key, idx, n, bits_for((uint64_t)nseg + 1), st);
-  if (e == hipSuccess) e = hipMalloc((void**)&first, (nseg + 2) * 8);
+  if (e == hipSuccess) e = first.alloc(nseg + 2);
   if (e == hipSuccess) e = hipMemsetAsync(first, 0xff, (nseg + 2) * 8, st);
-  if (e != hipSuccess) goto done;
-  hipLaunchKernelGGL(k_key_first, grid1(n), dim3(256), 0, st, n, key, first);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_key_first, grid1(n), dim3(256), 0, st, n, key.p, first.p);
   e = hipMemcpyAsync(hfirst.data(), first, (nseg + 1) * 8, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) goto done;
-  {
-    // end of key q = start of the next present key, or n
-    hfirst[nseg + 1] = n;
-    std::vector<int64_t> start(nseg + 2, n);
-    for (int q = nseg; q >= 0; --q) start[q] = hfirst[q] >= 0 ? hfirst[q] : start[q + 1];
-    nloc = start[1];
-    for (int q = 0; q < nseg; ++q) (*cnt)[q] = start[q + 2] - start[q + 1];
-  }
-  if (n - nloc > 0) {
-    const int64_t nr = n - nloc;
-    e = hipMalloc((void**)sI, nr * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)sJ, nr * 8);
-    if (e == hipSuccess) e = hipMalloc(sV, nr * S);
-    if (e != hipSuccess) goto done;
+  if (e != hipSuccess) return e;
+  // end of key q = start of the next present key, or n
+  hfirst[nseg + 1] = n;
+  std::vector<int64_t> start(nseg + 2, n);
+  for (int q = nseg; q >= 0; --q) start[q] = hfirst[q] >= 0 ? hfirst[q] : start[q + 1];
+  const int64_t nloc = start[1], nr = n - nloc;
+  for (int q = 0; q < nseg; ++q) (*cnt)[q] = start[q + 2] - start[q + 1];
+  if (nr > 0) {
+    e = out->I.alloc(nr);
+    if (e == hipSuccess) e = out->J.alloc(nr);
+    if (e == hipSuccess) e = out->V.alloc(nr * S);
+    if (e != hipSuccess) return e;
+    out->n = nr;
     switch (dtype) {
-      case PA_F32: coo_pack_t<float>(nr, idx + nloc, I, J, V, zero_src, *sI, *sJ, *sV, st); break;
-      case PA_F64: coo_pack_t<double>(nr, idx + nloc, I, J, V, zero_src, *sI, *sJ, *sV, st); break;
-      case PA_C64: coo_pack_t<c64>(nr, idx + nloc, I, J, V, zero_src, *sI, *sJ, *sV, st); break;
-      case PA_C128: coo_pack_t<c128>(nr, idx + nloc, I, J, V, zero_src, *sI, *sJ, *sV, st); break;
+      case PA_F32: coo_pack_t<float>(nr, idx.p + nloc, in.I, in.J, in.V, zero_src, out->I, out->J, out->V, st); break;
+      case PA_F64: coo_pack_t<double>(nr, idx.p + nloc, in.I, in.J, in.V, zero_src, out->I, out->J, out->V, st); break;
+      case PA_C64: coo_pack_t<c64>(nr, idx.p + nloc, in.I, in.J, in.V, zero_src, out->I, out->J, out->V, st); break;
+      case PA_C128: coo_pack_t<c128>(nr, idx.p + nloc, in.I, in.J, in.V, zero_src, out->I, out->J, out->V, st); break;
     }
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(st);
   }
-done:
-  if (first) (void)hipFree(first);
   return e;
-}
-
-// One part's send side.  Outputs (device, owned by the caller): *sI, *sJ,
-// *sV (the sent triplets, segment after segment) and cnt[0..nseg) on the
-// host.  Returns 1 when a row gid is not a local id of rows (KeyError), 2
-// when a ghost row's owner has no receive segment (KeyError).
-int coo_assemble_pack(int dtype, int64_t n, const int64_t* I, const int64_t* J, void* V, const uint64_t* sgid,
-                      const int64_t* slid, int64_t nl, const std::vector<int32_t>& lid_to_ohid, int nseg,
-                      const int32_t* d_lids_rcv,
-                      const std::vector<int64_t>& ptrs_rcv, int64_t** sI, int64_t** sJ, void** sV,
-                      std::vector<int64_t>* cnt, hipStream_t st) {
-  *sI = nullptr; *sJ = nullptr; *sV = nullptr;
-  cnt->assign(nseg, 0);
-  if (n <= 0) return 0;
-  hipError_t e = hipSuccess;
-  int32_t* sol = nullptr;
-  int64_t *dptrs = nullptr, *idx = nullptr;
-  uint64_t* key = nullptr;
-  int* bad = nullptr;
-  int hbad = 0, rc = 0;
-  const int64_t nslots = ptrs_rcv.empty() ? 0 : ptrs_rcv.back();
-  {
-    // -1: owned lid, -2: ghost lid (k_seg_of_lid then sets its segment)
-    std::vector<int32_t> hs(nl > 0 ? nl : 1, -1);
-    for (int64_t l = 0; l < nl; ++l) hs[l] = lid_to_ohid[l] > 0 ? -1 : -2;
-    e = hipMalloc((void**)&sol, hs.size() * 4);
-    if (e == hipSuccess) e = copy_sync(sol, hs.data(), hs.size() * 4, hipMemcpyHostToDevice, st);
-  }
-  if (e == hipSuccess && nslots > 0) e = hipMalloc((void**)&dptrs, ptrs_rcv.size() * 8);
-  if (e == hipSuccess && nslots > 0)
-    e = hipMemcpyAsync(dptrs, ptrs_rcv.data(), ptrs_rcv.size() * 8, hipMemcpyHostToDevice, st);
-  if (e != hipSuccess) goto done;
-  if (nslots > 0) hipLaunchKernelGGL(k_seg_of_lid, grid1(nslots), dim3(256), 0, st, nslots, d_lids_rcv, dptrs, nseg, sol);
-  e = hipMalloc((void**)&key, n * 8);
-  if (e == hipSuccess) e = hipMalloc((void**)&idx, n * 8);
-  if (e == hipSuccess) e = hipMalloc((void**)&bad, sizeof(int));
-  if (e == hipSuccess) e = hipMemsetAsync(bad, 0, sizeof(int), st);
-  if (e != hipSuccess) goto done;
-  hipLaunchKernelGGL(k_coo_seg, grid1(n), dim3(256), 0, st, n, I, sgid, slid, nl, sol, key, idx, bad);
-  e = hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) goto done;
-  if (hbad) { rc = hbad; goto done; }  // 1: unknown gid, 2: ghost row without a segment
-  e = coo_pack_by_key(dtype, n, I, J, V, key, idx, nseg, true, sI, sJ, sV, cnt, st);
-done:
-  for (void* p : {(void*)sol, (void*)dptrs, (void*)idx, (void*)key, (void*)bad})
-    if (p) (void)hipFree(p);
-  if (e != hipSuccess || rc) {
-    for (void** p : {(void**)sI, (void**)sJ, sV})
-      if (*p) { (void)hipFree(*p); *p = nullptr; }
-    return e != hipSuccess ? -1 : rc;
-  }
-  return 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -807,64 +698,64 @@ static void coo_xseg_t(int64_t n, const int64_t* I, void* V, const uint64_t* sgi
                      bad);
 }
 
-// One part's send side of exchange!.  Outputs as coo_assemble_pack: *sI, *sJ,
-// *sV (the sent triplets, segment after segment; device, owned by the
-// caller) and cnt[0..nseg) on the host, nseg = length(parts_snd).  Every lid
-// of d_lids_snd is below nl (checked by the caller).  Returns 1 when a row
-// gid is not a local id of rows (KeyError); ghost rows met before that may
-// already hold zero, as the reference leaves I half converted.
-int coo_exchange_pack(int dtype, int64_t n, const int64_t* I, const int64_t* J, void* V, const uint64_t* sgid,
-                      const int64_t* slid, int64_t nl, const std::vector<int32_t>& lid_to_ohid, int nseg,
-                      const int32_t* d_lids_snd, const std::vector<int64_t>& ptrs_snd, int64_t** sI, int64_t** sJ,
-                      void** sV, std::vector<int64_t>* cnt, hipStream_t st) {
-  *sI = nullptr; *sJ = nullptr; *sV = nullptr;
+// One part's send side of assemble! (to_ghosts = false, side = the
+// exchanger's rcv list: the triplets of the ghost rows go to the rows'
+// owners and become zero here) or exchange! (to_ghosts = true, side = its
+// snd list: the triplets of the rows that neighbours hold as ghosts).
+// Outputs: *out (the sent triplets, segment after segment) and
+// cnt[0..nseg) on the host, nseg = the side's neighbours.  Every lid of the
+// side is below nl (checked by the caller).  Returns 1 when a row gid is not
+// a local id of rows (KeyError; exchange!: ghost rows met before that may
+// already hold zero, as the reference leaves I half converted), 2 when a
+// ghost row's owner has no receive segment (assemble!, KeyError).
+int coo_send_pack(bool to_ghosts, int dtype, const CooList& in, const uint64_t* sgid, const int64_t* slid, int64_t nl,
+                  const std::vector<int32_t>& lid_to_ohid, const XchgSide& side, CooList* out,
+                  std::vector<int64_t>* cnt, hipStream_t st) {
+  const int nseg = (int)side.parts.size();
+  const int64_t n = in.n;
+  *out = CooList{};
   cnt->assign(nseg, 0);
   if (n <= 0) return 0;
-  hipError_t e = hipSuccess;
-  int32_t* sol = nullptr;
-  int64_t *dptrs = nullptr, *idx = nullptr;
-  uint64_t* key = nullptr;
-  int* bad = nullptr;
-  int hbad = 0, rc = 0;
-  const int64_t nslots = ptrs_snd.empty() ? 0 : ptrs_snd.back();
-  {
-    // 0: owned lid, -1: ghost lid (k_snd_seg_of_lid then raises the listed ones)
-    std::vector<int32_t> hs(nl > 0 ? nl : 1, 0);
-    for (int64_t l = 0; l < nl; ++l) hs[l] = lid_to_ohid[l] > 0 ? 0 : -1;
-    e = hipMalloc((void**)&sol, hs.size() * 4);
-    if (e == hipSuccess) e = copy_sync(sol, hs.data(), hs.size() * 4, hipMemcpyHostToDevice, st);
+  DevBuf<int32_t> sol;
+  DevBuf<int64_t> dptrs, idx;
+  DevBuf<uint64_t> key;
+  DevBuf<int> bad;
+  int hbad = 0;
+  const int64_t nslots = side.ptrs.empty() ? 0 : side.ptrs.back();
+  // a lid's mark before the side's slots are visited.  assemble!: -1 owned,
+  // -2 ghost (k_seg_of_lid then sets its segment); exchange!: 0 owned, -1
+  // ghost (k_snd_seg_of_lid then raises the listed ones)
+  const int32_t owned = to_ghosts ? 0 : -1, ghost = owned - 1;
+  std::vector<int32_t> hs(nl > 0 ? nl : 1, owned);
+  for (int64_t l = 0; l < nl; ++l) hs[l] = lid_to_ohid[l] > 0 ? owned : ghost;
+  PA_HIP_OR(sol.alloc(hs.size()), -1);
+  PA_HIP_OR(copy_sync(sol, hs.data(), hs.size() * 4, hipMemcpyHostToDevice, st), -1);
+  if (nslots > 0) {
+    PA_HIP_OR(dptrs.alloc(side.ptrs.size()), -1);
+    PA_HIP_OR(hipMemcpyAsync(dptrs, side.ptrs.data(), side.ptrs.size() * 8, hipMemcpyHostToDevice, st), -1);
+    if (to_ghosts)
+      hipLaunchKernelGGL(k_snd_seg_of_lid, grid1(nslots), dim3(256), 0, st, nslots, side.lids.p, dptrs.p, nseg, sol.p);
+    else
+      hipLaunchKernelGGL(k_seg_of_lid, grid1(nslots), dim3(256), 0, st, nslots, side.lids.p, dptrs.p, nseg, sol.p);
   }
-  if (e == hipSuccess && nslots > 0) e = hipMalloc((void**)&dptrs, ptrs_snd.size() * 8);
-  if (e == hipSuccess && nslots > 0)
-    e = hipMemcpyAsync(dptrs, ptrs_snd.data(), ptrs_snd.size() * 8, hipMemcpyHostToDevice, st);
-  if (e != hipSuccess) goto done;
-  if (nslots > 0)
-    hipLaunchKernelGGL(k_snd_seg_of_lid, grid1(nslots), dim3(256), 0, st, nslots, d_lids_snd, dptrs, nseg, sol);
-  e = hipMalloc((void**)&key, n * 8);
-  if (e == hipSuccess) e = hipMalloc((void**)&idx, n * 8);
-  if (e == hipSuccess) e = hipMalloc((void**)&bad, sizeof(int));
-  if (e == hipSuccess) e = hipMemsetAsync(bad, 0, sizeof(int), st);
-  if (e != hipSuccess) goto done;
-  switch (dtype) {
-    case PA_F32: coo_xseg_t<float>(n, I, V, sgid, slid, nl, sol, key, idx, bad, st); break;
-    case PA_F64: coo_xseg_t<double>(n, I, V, sgid, slid, nl, sol, key, idx, bad, st); break;
-    case PA_C64: coo_xseg_t<c64>(n, I, V, sgid, slid, nl, sol, key, idx, bad, st); break;
-    case PA_C128: coo_xseg_t<c128>(n, I, V, sgid, slid, nl, sol, key, idx, bad, st); break;
+  PA_HIP_OR(key.alloc(n), -1);
+  PA_HIP_OR(idx.alloc(n), -1);
+  PA_HIP_OR(bad.alloc(1), -1);
+  PA_HIP_OR(hipMemsetAsync(bad, 0, sizeof(int), st), -1);
+  if (!to_ghosts) {
+    hipLaunchKernelGGL(k_coo_seg, grid1(n), dim3(256), 0, st, n, in.I.p, sgid, slid, nl, sol.p, key.p, idx.p, bad.p);
+  } else {
+    switch (dtype) {
+      case PA_F32: coo_xseg_t<float>(n, in.I, in.V, sgid, slid, nl, sol, key, idx, bad, st); break;
+      case PA_F64: coo_xseg_t<double>(n, in.I, in.V, sgid, slid, nl, sol, key, idx, bad, st); break;
+      case PA_C64: coo_xseg_t<c64>(n, in.I, in.V, sgid, slid, nl, sol, key, idx, bad, st); break;
+      case PA_C128: coo_xseg_t<c128>(n, in.I, in.V, sgid, slid, nl, sol, key, idx, bad, st); break;
+    }
   }
-  e = hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) goto done;
-  if (hbad) { rc = 1; goto done; }
-  e = coo_pack_by_key(dtype, n, I, J, V, key, idx, nseg, false, sI, sJ, sV, cnt, st);
-done:
-  for (void* p : {(void*)sol, (void*)dptrs, (void*)idx, (void*)key, (void*)bad})
-    if (p) (void)hipFree(p);
-  if (e != hipSuccess || rc) {
-    for (void** p : {(void**)sI, (void**)sJ, sV})
-      if (*p) { (void)hipFree(*p); *p = nullptr; }
-    return e != hipSuccess ? -1 : rc;
-  }
-  return 0;
+  PA_HIP_OR(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, st), -1);
+  PA_HIP_OR(hipStreamSynchronize(st), -1);
+  if (hbad) return hbad;  // 1: unknown gid, 2: ghost row without a segment (assemble! only)
+  return coo_pack_by_key(dtype, in, key, idx, nseg, !to_ghosts, out, cnt, st) == hipSuccess ? 0 : -1;
 }
 
 }  // namespace pa

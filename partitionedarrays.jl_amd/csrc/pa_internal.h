@@ -414,98 +414,6 @@ struct TuneScope {
   const pa::Knobs* prev;
 };
 
-struct pa_index {
-  pa_ctx* ctx = nullptr;
-  int64_t nlids = 0, noids = 0, nhids = 0;
-  bool own_contig = true;    // oid_to_lid == 0..noids-1 (0-based)
-  bool ghost_contig = true;  // hid_to_lid == noids..nlids-1
-  int32_t* d_oid_to_lid = nullptr;  // 0-based, null when own_contig
-  int32_t* d_hid_to_lid = nullptr;  // 0-based, null when ghost_contig
-  std::vector<int32_t> h_oid_to_lid;  // 0-based host copies
-  std::vector<int32_t> h_hid_to_lid;
-  std::vector<int32_t> h_lid_to_ohid;  // reference's lid_to_ohid (1-based ±)
-  // gid → lid table (pa_index_set_gids): gids sorted ascending, their lids
-  uint64_t* d_sgid = nullptr;
-  int64_t* d_slid = nullptr;
-  bool has_gids = false;
-};
-
-// Ordered combine plan: for each distinct target lid, the buffer positions
-// that land on it, ascending (= the reference's unpack loop order).
-struct pa_combine_plan {
-  int64_t ntargets = 0;
-  bool unique = true;                // every lid at most once → plain scatter
-  int32_t* d_target = nullptr;       // distinct target lids (0-based)
-  int32_t* d_ptr = nullptr;          // ntargets+1
-  int32_t* d_pos = nullptr;          // buffer positions
-};
-
-// Pull table of one exchange direction (parts of one process): receive slot
-// p of this part reads bases[bid[p]][elem[p]] — a sender's send buffer, or
-// this part's own receive buffer for segments that came over RCCL.
-struct pa_pull {
-  bool built = false;
-  bool ok = false;                   // false: peers not reachable, use staging copies
-  std::vector<const void*> key;      // the local senders (exchanger ids) and buffers the table was built for
-  int32_t* d_bid = nullptr;
-  int64_t* d_elem = nullptr;
-  void** d_bases = nullptr;
-};
-
-struct pa_xchg {
-  pa_ctx* ctx = nullptr;
-  uint64_t id = 0;                             // unique per exchanger of the process (cache keys)
-  pa_pull pull[2];                             // [0] forward, [1] reverse
-  // direct pull of mul! over parts sharing one stream pair (spmv_grouped):
-  // receive slot p reads x of the call's part bid[p] at lid elem[p] (the
-  // sender's lids_snd entry), no pack, no send buffer, no cross-stream event
-  pa_pull direct;
-  std::vector<int32_t> h_lids_snd;             // 0-based host copy (vector exchangers)
-  std::vector<int32_t> parts_rcv, parts_snd;   // 1-based
-  std::vector<int64_t> ptrs_rcv, ptrs_snd;     // 0-based offsets, size n+1
-  int64_t n_rcv_data = 0, n_snd_data = 0;
-  int64_t max_lid = -1;                        // 0-based, over both lists
-  int32_t* d_lids_rcv = nullptr;               // 0-based
-  int32_t* d_lids_snd = nullptr;
-  void* d_buf_rcv = nullptr;                   // 16 B per slot
-  void* d_buf_snd = nullptr;
-  // the barrier issue of stream-pair mul! (spmv_impl): a second forward send
-  // buffer, used every other call, and the pull table against the senders'
-  // second buffers; the last barrier call these exchangers took part in
-  // (key of its exchanger set, its sequence number, the buffer it packed)
-  void* d_buf_snd2 = nullptr;
-  pa_pull pull_alt;
-  uint64_t fast_key = 0, fast_seq = 0;
-  int fast_parity = 0;
-  pa_combine_plan plan_fwd;   // unpack targets = lids_rcv
-  pa_combine_plan plan_rev;   // unpack targets = lids_snd (reverse/assemble)
-};
-
-constexpr size_t kVecPad = 64;  // bytes before and after a vector's values (pa_vec_create)
-
-// COO triplets of one part on the device (global row/column ids, Int64),
-// the input of async_assemble!(I, J, V, rows) and PSparseMatrix(I, J, V, …)
-struct pa_coo {
-  pa_ctx* ctx = nullptr;
-  int dtype = PA_F64;
-  int64_t n = 0;
-  int64_t* d_I = nullptr;
-  int64_t* d_J = nullptr;
-  void* d_V = nullptr;
-};
-
-struct pa_vec {
-  pa_ctx* ctx = nullptr;
-  int dtype = PA_F64;
-  int64_t n = 0;
-  void* d = nullptr;      // the values (base + kVecPad)
-  void* base = nullptr;   // the allocation (owned; null for views)
-};
-
-// int32 words of a pattern slice's descriptor (dedup_patterns, SPMV_DESC):
-// 4 header words + the slice's H/64 64-bit mask words, a power of two
-constexpr int desc_words(int R) { return R <= 2 ? 8 : 16; }
-
 namespace pa {
 // A device array and its owner (move-only).  It converts to its pointer, so
 // launches and copies take it as they would the raw pointer.
@@ -548,7 +456,115 @@ inline hipError_t download(std::vector<T>& h, const T* d, size_t n, hipStream_t 
   h.resize(n);
   return hipMemcpyAsync(h.data(), d, n * sizeof(T), hipMemcpyDeviceToHost, st);
 }
+}  // namespace pa
 
+struct pa_index {
+  pa_ctx* ctx = nullptr;
+  int64_t nlids = 0, noids = 0, nhids = 0;
+  bool own_contig = true;    // oid_to_lid == 0..noids-1 (0-based)
+  bool ghost_contig = true;  // hid_to_lid == noids..nlids-1
+  pa::DevBuf<int32_t> d_oid_to_lid;  // 0-based, null when own_contig
+  pa::DevBuf<int32_t> d_hid_to_lid;  // 0-based, null when ghost_contig
+  std::vector<int32_t> h_oid_to_lid;  // 0-based host copies
+  std::vector<int32_t> h_hid_to_lid;
+  std::vector<int32_t> h_lid_to_ohid;  // reference's lid_to_ohid (1-based ±)
+  // gid → lid table (pa_index_set_gids): gids sorted ascending, their lids
+  pa::DevBuf<uint64_t> d_sgid;
+  pa::DevBuf<int64_t> d_slid;
+  bool has_gids = false;
+};
+
+// Ordered combine plan: for each distinct target lid, the buffer positions
+// that land on it, ascending (= the reference's unpack loop order).
+struct pa_combine_plan {
+  int64_t ntargets = 0;
+  bool unique = true;                // every lid at most once → plain scatter
+  pa::DevBuf<int32_t> d_target;      // distinct target lids (0-based)
+  pa::DevBuf<int32_t> d_ptr;         // ntargets+1
+  pa::DevBuf<int32_t> d_pos;         // buffer positions
+};
+
+// Pull table of one exchange direction (parts of one process): receive slot
+// p of this part reads bases[bid[p]][elem[p]] — a sender's send buffer, or
+// this part's own receive buffer for segments that came over RCCL.
+struct pa_pull {
+  bool built = false;
+  bool ok = false;                   // false: peers not reachable, use staging copies
+  std::vector<const void*> key;      // the local senders (exchanger ids) and buffers the table was built for
+  pa::DevBuf<int32_t> d_bid;
+  pa::DevBuf<int64_t> d_elem;
+  pa::DevBuf<void*> d_bases;
+};
+
+namespace pa {
+// One neighbour list of an exchanger
+struct XchgSide {
+  std::vector<int32_t> parts;   // 1-based
+  std::vector<int64_t> ptrs;    // 0-based offsets, size n+1
+  int64_t n = 0;                // slots
+  DevBuf<int32_t> lids;         // 0-based
+  DevBuf<void> buf;             // 16 B per slot
+  pa_combine_plan plan;         // unpack targets = this side's lids
+};
+// COO triplets on the device: global row/column ids (Int64) and values
+struct CooList {
+  DevBuf<int64_t> I, J;
+  DevBuf<void> V;
+  int64_t n = 0;
+};
+}  // namespace pa
+
+struct pa_xchg {
+  pa_ctx* ctx = nullptr;
+  uint64_t id = 0;                             // unique per exchanger of the process (cache keys)
+  pa_pull pull[2];                             // [0] forward, [1] reverse
+  // direct pull of mul! over parts sharing one stream pair (spmv_grouped):
+  // receive slot p reads x of the call's part bid[p] at lid elem[p] (the
+  // sender's snd.lids entry), no pack, no send buffer, no cross-stream event
+  pa_pull direct;
+  std::vector<int32_t> h_lids_snd;             // 0-based host copy (vector exchangers)
+  // forward (dir 0, exchange!): snd's slots travel to the neighbours' rcv;
+  // reverse (dir 1, assemble!): rcv's slots travel to the neighbours' snd
+  pa::XchgSide rcv, snd;
+  // the side a transfer in direction dir lands on / leaves from
+  pa::XchgSide& into(int dir) { return dir ? snd : rcv; }
+  const pa::XchgSide& into(int dir) const { return dir ? snd : rcv; }
+  pa::XchgSide& from(int dir) { return into(1 - dir); }
+  const pa::XchgSide& from(int dir) const { return into(1 - dir); }
+  int64_t max_lid = -1;                        // 0-based, over both lists
+  // the barrier issue of stream-pair mul! (spmv_impl): a second forward send
+  // buffer, used every other call, and the pull table against the senders'
+  // second buffers; the last barrier call these exchangers took part in
+  // (key of its exchanger set, its sequence number, the buffer it packed)
+  pa::DevBuf<void> buf_snd2;
+  pa_pull pull_alt;
+  uint64_t fast_key = 0, fast_seq = 0;
+  int fast_parity = 0;
+};
+
+constexpr size_t kVecPad = 64;  // bytes before and after a vector's values (pa_vec_create)
+
+// COO triplets of one part on the device, the input of
+// async_assemble!(I, J, V, rows) and PSparseMatrix(I, J, V, …)
+struct pa_coo {
+  pa_ctx* ctx = nullptr;
+  int dtype = PA_F64;
+  pa::CooList l;
+};
+
+struct pa_vec {
+  pa_ctx* ctx = nullptr;
+  int dtype = PA_F64;
+  int64_t n = 0;
+  void* d = nullptr;        // the values (base + kVecPad)
+  pa::DevBuf<void> base;    // the allocation (null for views)
+};
+
+// int32 words of a pattern slice's descriptor (dedup_patterns, SPMV_DESC):
+// 4 header words + the slice's H/64 64-bit mask words, a power of two
+constexpr int desc_words(int R) { return R <= 2 ? 8 : 16; }
+
+namespace pa {
 // The kind of a slice of the main structure as the build records it
 // (pa_mat::h_kind, pa_mat::d_kind; k_pattern_detect, k_delta16 and k_u_fill
 // write and read the numbers).  The device copy holds kBkInt32, kBkPattern
