@@ -50,6 +50,7 @@ typedef struct pa_xchg pa_xchg;
 typedef struct pa_vec pa_vec;
 typedef struct pa_mat pa_mat;
 typedef struct pa_coo pa_coo;
+typedef struct pa_event pa_event; /* completion of one call's work for one part */
 
 /* ---- errors / library info ------------------------------------------- */
 const char* pa_last_error(void);
@@ -628,6 +629,41 @@ int pa_mat_cg_choice(const pa_mat* A, int* choice);
 int pa_exchange_all(int n, pa_vec* const v[], pa_xchg* const xg[],
                     const pa_index* const idx[], int op, int reverse,
                     int zero_ghosts);
+
+/* ---- async exchange and completion handles -------------------------------
+ * t = async_exchange!(…) / async_assemble!(…) (Interfaces.jl:349-401,
+ * 2071-2106, 2375-2404): the same values in the same combine order as
+ * pa_exchange_all / pa_mat_exchange_all, but all of part i's work (pack,
+ * transport, unpack, zeroed ghosts / sent values) runs on part i's comm
+ * stream, and done[i] completes behind the last of it.  The call returns at
+ * once.  Part i's work starts after (a) everything enqueued so far on its
+ * context, (b) after[i] when given (after: NULL, or n entries, each NULL or
+ * an event of any context or device: the t0 of Interfaces.jl:369-373 without
+ * a host wait), and (c) every earlier call that still uses the exchanger
+ * buffers of part i or of its local peers.  Work enqueued later on the
+ * compute stream does not wait for the call, except a later call on the same
+ * exchanger, a context joined with pa_ctx_wait_event, and pa_ctx_sync.  From
+ * the call until the wait or join the values belong to the call.  A failed
+ * call leaves no handle in done.                                            */
+int pa_exchange_all_async(int n, pa_vec* const v[], pa_xchg* const xg[],
+                          const pa_index* const idx[], int op, int reverse,
+                          int zero_ghosts, pa_event* const after[],
+                          pa_event* done[]);
+int pa_mat_exchange_all_async(int n, pa_mat* const A[], pa_xchg* const xg[],
+                              int op, int reverse, int zero_sent,
+                              pa_event* const after[], pa_event* done[]);
+/* An event behind everything enqueued so far on ctx, on both its streams
+ * (e.g. a mul! whose result an exchange takes as after[i]).               */
+int pa_event_record(pa_ctx* ctx, pa_event** out);
+/* *done = 1 once the event's work has finished, else 0; never blocks.     */
+int pa_event_query(const pa_event* ev, int* done);
+/* Blocks the host until this event's work has finished (nothing else).    */
+int pa_event_wait(pa_event* ev);
+/* Device-side join: what is enqueued on ctx's compute stream from now on
+ * runs after the event; the host does not wait.                           */
+int pa_ctx_wait_event(pa_ctx* ctx, const pa_event* ev);
+/* Frees the handle; legal while its work is pending (the work goes on).   */
+int pa_event_destroy(pa_event* ev);
 
 /* dot(a,b) (Interfaces.jl:1985-1992) → sum over parts, folded in part
  * order as reduce(+, …; init=0) (Interfaces.jl:221-238).  result: host

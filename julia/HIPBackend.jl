@@ -426,8 +426,61 @@ end
 const HIPVector{T} = PVector{T,<:HIPData}
 const HIPMatrix{T} = PSparseMatrix{T,<:HIPData}
 
-# the tasks async operations hand back: the device work is already enqueued
-# (stream-ordered); waiting on a task synchronises its part's streams
+# ---- completion handles (pa_event) ------------------------------------------
+# async_exchange! / async_assemble! on vectors and matrices return one
+# unscheduled task per part that waits on that call's own event
+# (pa_event_wait): the exchange ran on the part's comm stream and nothing else
+# is waited for.  The holder frees the event when it is collected
+# (pa_event_destroy is legal while the work is pending).
+mutable struct EventHolder
+  h::Ptr{Cvoid}
+  function EventHolder(h::Ptr{Cvoid})
+    e = new(h)
+    finalizer(e) do x
+      x.h == C_NULL || ccall((:pa_event_destroy, libpa), Cint, (Ptr{Cvoid},), x.h)
+      x.h = C_NULL
+    end
+    e
+  end
+end
+# the tasks this binding created → their events: such a task coming back as
+# t0 (Interfaces.jl:369-373) goes to the library as `after`, a device-side
+# wait; its closure keeps the holder alive as long as the task lives
+const TASK_EVENTS = WeakKeyDict{Task,EventHolder}()
+
+function _event_tasks(done::Vector{Ptr{Cvoid}}, a::HIPData)
+  tasks = map(done) do h
+    ev = EventHolder(h)
+    t = @task check(ccall((:pa_event_wait, libpa), Cint, (Ptr{Cvoid},), ev.h))
+    TASK_EVENTS[t] = ev
+    t
+  end
+  HIPData(tasks, a.ctxs, a.backend)
+end
+# t0 → (the `after` array, the holders to keep alive through the call); a
+# task of any other origin is scheduled and waited on the host
+function _after(t0::HIPData)
+  holders = EventHolder[]
+  after = map(t0.parts) do t
+    ev = get(TASK_EVENTS, t, nothing)
+    if ev === nothing
+      istaskstarted(t) || schedule(t)
+      wait(t)
+      C_NULL
+    else
+      push!(holders, ev)
+      ev.h
+    end
+  end
+  convert(Vector{Ptr{Cvoid}}, after), holders
+end
+function _after(t0::AbstractPData)
+  _wait_all(t0)
+  fill(C_NULL, num_parts(t0)), EventHolder[]
+end
+
+# the tasks of the COO forms, which size their outputs on the host and have
+# completed when they return: waiting on one synchronises its part's streams
 function _done_tasks(a::HIPData)
   tasks = map(a.ctxs) do c
     @task check(ccall((:pa_ctx_sync, libpa), Cint, (Ptr{Cvoid},), c.h))
@@ -467,6 +520,12 @@ function Base.:*(a::HIPMatrix{Ta}, b::HIPVector{Tb}) where {Ta,Tb}   # Interface
 end
 
 # ---- exchange!/assemble! (Interfaces.jl:2071-2106, 2375-2404) --------------
+# async_exchange! / async_assemble! call the _async entries: the work runs on
+# the parts' comm streams and each returned task waits on its own event, so
+# the reference's blocking exchange! / assemble! (schedule + wait over those
+# tasks, 453-458) wait for that call alone.  _exchange_all / _mat_exchange_all
+# are the library's blocking forms in compute-stream order (no task, nothing
+# to wait on before the next call on these parts).
 function _exchange_all(v::HIPVector, op::Integer, rev::Integer, zero_ghosts::Integer)
   vv, vi, xg = dev_vec(v), dev_idx(v.rows), dev_xchg(v.rows)
   check(ccall((:pa_exchange_all, libpa), Cint,
@@ -474,18 +533,25 @@ function _exchange_all(v::HIPVector, op::Integer, rev::Integer, zero_ghosts::Int
               length(vv), vv, xg, vi, op, rev, zero_ghosts))
   mark_device_newer!(v)
 end
+function _exchange_all_async(v::HIPVector, op::Integer, rev::Integer, zero_ghosts::Integer, t0::AbstractPData)
+  vv, vi, xg = dev_vec(v), dev_idx(v.rows), dev_xchg(v.rows)
+  after, holders = _after(t0)
+  done = fill(C_NULL, length(vv))
+  GC.@preserve holders check(ccall((:pa_exchange_all_async, libpa), Cint,
+              (Cint, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Cint, Cint, Cint,
+               Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}),
+              length(vv), vv, xg, vi, op, rev, zero_ghosts, after, done))
+  mark_device_newer!(v)
+  _event_tasks(done, v.values)
+end
 function async_exchange!(a::HIPVector{T}, t0::AbstractPData=PartitionedArrays._empty_tasks(a.rows.exchanger.parts_rcv)) where {T<:DeviceEltype}
-  _wait_all(t0)
-  _exchange_all(a, 0, 0, 0)
-  _done_tasks(a.values)
+  _exchange_all_async(a, 0, 0, 0, t0)
 end
 function async_assemble!(a::HIPVector{T}, t0::AbstractPData=PartitionedArrays._empty_tasks(a.rows.exchanger.parts_rcv)) where {T<:DeviceEltype}
   async_assemble!(+, a, t0)
 end
 function async_assemble!(::typeof(+), a::HIPVector{T}, t0::AbstractPData=PartitionedArrays._empty_tasks(a.rows.exchanger.parts_rcv)) where {T<:DeviceEltype}
-  _wait_all(t0)
-  _exchange_all(a, 1, 1, 1)   # reverse(exchanger), +, then ghost values = 0
-  _done_tasks(a.values)
+  _exchange_all_async(a, 1, 1, 1, t0)   # reverse(exchanger), +, then ghost values = 0
 end
 
 function _mat_exchange_all(a::HIPMatrix, op::Integer, rev::Integer, zero_sent::Integer)
@@ -494,15 +560,21 @@ function _mat_exchange_all(a::HIPMatrix, op::Integer, rev::Integer, zero_sent::I
               (Cint, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Cint, Cint, Cint), length(A), A, mx, op, rev, zero_sent))
   mark_device_newer!(a)
 end
+function _mat_exchange_all_async(a::HIPMatrix, op::Integer, rev::Integer, zero_sent::Integer, t0::AbstractPData)
+  A, mx = dev_mat(a), dev_mat_xchg(a)
+  after, holders = _after(t0)
+  done = fill(C_NULL, length(A))
+  GC.@preserve holders check(ccall((:pa_mat_exchange_all_async, libpa), Cint,
+              (Cint, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Cint, Cint, Cint, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}),
+              length(A), A, mx, op, rev, zero_sent, after, done))
+  mark_device_newer!(a)
+  _event_tasks(done, a.values)
+end
 function async_exchange!(a::HIPMatrix{T}, t0::AbstractPData=PartitionedArrays._empty_tasks(a.exchanger.parts_rcv)) where {T<:DeviceEltype}
-  _wait_all(t0)
-  _mat_exchange_all(a, 0, 0, 0)
-  _done_tasks(a.values)
+  _mat_exchange_all_async(a, 0, 0, 0, t0)
 end
 function async_assemble!(::typeof(+), a::HIPMatrix{T}, t0::AbstractPData=PartitionedArrays._empty_tasks(a.exchanger.parts_rcv)) where {T<:DeviceEltype}
-  _wait_all(t0)
-  _mat_exchange_all(a, 1, 1, 1)
-  _done_tasks(a.values)
+  _mat_exchange_all_async(a, 1, 1, 1, t0)
 end
 async_assemble!(a::HIPMatrix{T}, t0::AbstractPData=PartitionedArrays._empty_tasks(a.exchanger.parts_rcv)) where {T<:DeviceEltype} =
   async_assemble!(+, a, t0)

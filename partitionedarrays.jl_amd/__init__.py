@@ -17,11 +17,12 @@ from .prange import (Exchanger, IndexSet, PRange, add_gids, add_gids_, discover_
                      empty_exchanger, exchanger_from_ids, hids_are_equal, index_range,
                      lids_are_equal, oids_are_equal, prange_cartesian, prange_from_partition,
                      prange_linear, prange_noids, to_lids_)
-from .device import DeviceMatrix, HIPBackend, HIPDistributedBackend, device_index  # noqa: F401
+from .device import DeviceMatrix, HIPBackend, HIPDistributedBackend, Task, device_index  # noqa: F401
 from .pvector import (COO, CSC, CSR, PSparseMatrix, PVector, assemble_, axmy_, axpy_, cg_, cg_update_,  # noqa: F401
                       compresscoo, copyto_, csr_init, sparsecsr, fillstored_, dot, exchange_, matvec, mul_, mul_dot_, norm, psum, rmul_,
                       sub_, xpby_)
 from .pvector import (Broadcasted, ExprProgram, abs2, all_, any_, assign_, conj, encode_expr, eq, euclidean,  # noqa: F401
                       isequal, materialize, maximum, minimum, ne, sqeuclidean)
+from .pvector import async_assemble_, async_exchange_, record, wait_all  # noqa: F401
 from .ptimers import PTimer  # noqa: F401
 from . import drivers  # noqa: F401

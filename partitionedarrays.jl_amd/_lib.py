@@ -127,6 +127,15 @@ _SIGS = {
                         C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.c_double, C.c_double, C.c_int64, C.c_int,
                         _i64p, C.POINTER(C.c_double), C.POINTER(C.c_double)],
     "pa_exchange_all": [C.c_int, C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.c_int, C.c_int, C.c_int],
+    "pa_exchange_all_async": [C.c_int, C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.c_int, C.c_int, C.c_int,
+                              C.POINTER(_p), C.POINTER(_p)],
+    "pa_mat_exchange_all_async": [C.c_int, C.POINTER(_p), C.POINTER(_p), C.c_int, C.c_int, C.c_int, C.POINTER(_p),
+                                  C.POINTER(_p)],
+    "pa_event_record": [_p, C.POINTER(_p)],
+    "pa_event_query": [_p, C.POINTER(C.c_int)],
+    "pa_event_wait": [_p],
+    "pa_ctx_wait_event": [_p, _p],
+    "pa_event_destroy": [_p],
     "pa_dot_all": [C.c_int, C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), _p],
     "pa_norm2_all": [C.c_int, C.POINTER(_p), C.POINTER(_p), _p],
     "pa_sum_all": [C.c_int, C.POINTER(_p), C.POINTER(_p), _p],

@@ -1232,15 +1232,16 @@ int check_lids(const pa_xchg* X, const pa_vec* v) {
   return 0;
 }
 
-// Before part i packs into its send buffer again, its s_main waits for the
-// previous exchange's reads of it: its own unpack and its local receivers'
-// pulls or copies (they record ev_recvd after them; for RCCL sends the
-// part's own ev_recvd covers them).
-int pre_pack_wait_part(int i, pa_xchg* const xg[], const LocalSet& L) {
+// Before part i packs into its send buffer again, the stream it packs on
+// (st; null: its s_main) waits for the previous exchange's reads of it: its
+// own unpack and its local receivers' pulls or copies (they record ev_recvd
+// after them; for RCCL sends the part's own ev_recvd covers them).
+int pre_pack_wait_part(int i, pa_xchg* const xg[], const LocalSet& L, hipStream_t st = nullptr) {
   xg[i]->fast_key = 0;  // the next barrier call of these exchangers waits too (spmv_impl)
   pa_ctx* c = xg[i]->ctx;
+  if (!st) st = c->s_main;
   HIPC(hipSetDevice(c->device));
-  HIPC(hipStreamWaitEvent(c->s_main, c->ev_recvd, 0));
+  HIPC(hipStreamWaitEvent(st, c->ev_recvd, 0));
   std::vector<hipEvent_t> seen{c->ev_recvd};
   for (const auto* lst : {&xg[i]->snd.parts, &xg[i]->rcv.parts})
     for (int32_t q : *lst) {
@@ -1249,7 +1250,7 @@ int pre_pack_wait_part(int i, pa_xchg* const xg[], const LocalSet& L) {
       const hipEvent_t e = xg[j]->ctx->ev_recvd;
       if (std::find(seen.begin(), seen.end(), e) != seen.end()) continue;  // parts_snd and parts_rcv overlap
       seen.push_back(e);
-      HIPC(hipStreamWaitEvent(c->s_main, e, 0));
+      HIPC(hipStreamWaitEvent(st, e, 0));
     }
   return 0;
 }
@@ -3824,11 +3825,14 @@ static int spmv_impl(int n, pa_mat* const A[], pa_vec* const y[], const pa_index
   return 0;
 }
 
-int pa_exchange_all(int n, pa_vec* const v[], pa_xchg* const xg[], const pa_index* const idx[], int op,
-                    int reverse, int zero_ghosts) {
+namespace {
+
+// The steps of exchange!(combine, values, exchanger) for part i on stream st:
+// pa_exchange_all issues them on the part's compute stream, the async entry
+// on its comm stream.
+int exchange_check(int n, pa_vec* const v[], pa_xchg* const xg[], int op) {
   CHECK_ARG(n >= 1 && v && xg && v[0], "null argument");
   CHECK_ARG(op == PA_REPLACE || op == PA_ADD, "invalid combine op");
-  TuneScope ts(v[0]->ctx);
   const int dt = v[0]->dtype;
   for (int i = 0; i < n; ++i) {
     CHECK_ARG(v[i] && xg[i], "null handle");
@@ -3836,31 +3840,212 @@ int pa_exchange_all(int n, pa_vec* const v[], pa_xchg* const xg[], const pa_inde
     CHECK_ARG(v[i]->ctx == xg[i]->ctx, "exchange!: vector and exchanger of different parts");
     if (check_lids(xg[i], v[i])) return -1;
   }
+  return 0;
+}
+
+int exchange_pack(int i, pa_vec* const v[], pa_xchg* const xg[], int dir, hipStream_t st) {
+  pa_ctx* c = xg[i]->ctx;
+  const XchgSide& s = xg[i]->from(dir);
+  HIPC(hipSetDevice(c->device));
+  launch_pack(v[i]->dtype, s.n, s.lids, v[i]->d, s.buf, st);
+  HIPC(hipEventRecord(c->ev_packed, st));
+  return 0;
+}
+
+// the unpack (unless the transport pulled into v) and assemble!'s zeroed ghosts
+int exchange_unpack(int i, pa_vec* const v[], pa_xchg* const xg[], const pa_index* const idx[], int op, int dir,
+                    bool pulled, int zero_ghosts, hipStream_t st) {
+  pa_ctx* c = xg[i]->ctx;
+  const XchgSide& r = xg[i]->into(dir);
+  const int dt = v[i]->dtype;
+  HIPC(hipSetDevice(c->device));
+  HIPC(hipStreamWaitEvent(st, c->ev_recvd, 0));
+  if (!pulled) launch_unpack(dt, r.n, r.lids, r.plan, op, r.buf, v[i]->d, st);
+  if (zero_ghosts) {
+    CHECK_ARG(idx && idx[i] && idx[i]->nlids == v[i]->n, "assemble!: index set of the vector required");
+    unsigned char z[16] = {0};
+    launch_fill(dt, idx[i]->nhids, idx[i]->noids, idx[i]->d_hid_to_lid, v[i]->d, z, st);
+  }
+  return 0;
+}
+
+}  // namespace
+
+int pa_exchange_all(int n, pa_vec* const v[], pa_xchg* const xg[], const pa_index* const idx[], int op,
+                    int reverse, int zero_ghosts) {
+  if (exchange_check(n, v, xg, op)) return -1;
+  TuneScope ts(v[0]->ctx);
+  const int dt = v[0]->dtype;
   const int dir = reverse ? 1 : 0;
   if (pre_pack_wait(n, xg)) return -1;
-  for (int i = 0; i < n; ++i) {
-    pa_ctx* c = xg[i]->ctx;
-    const XchgSide& s = xg[i]->from(dir);
-    HIPC(hipSetDevice(c->device));
-    launch_pack(dt, s.n, s.lids, v[i]->d, s.buf, c->s_main);
-    HIPC(hipEventRecord(c->ev_packed, c->s_main));
-  }
+  for (int i = 0; i < n; ++i)
+    if (exchange_pack(i, v, xg, dir, xg[i]->ctx->s_main)) return -1;
   HIPC(hipGetLastError());
   bool pulled = false;
   if (transport(n, xg, dt, dir, op, v, &pulled)) return -1;
-  for (int i = 0; i < n; ++i) {
-    pa_ctx* c = xg[i]->ctx;
-    const XchgSide& r = xg[i]->into(dir);
-    HIPC(hipSetDevice(c->device));
-    HIPC(hipStreamWaitEvent(c->s_main, c->ev_recvd, 0));
-    if (!pulled) launch_unpack(dt, r.n, r.lids, r.plan, op, r.buf, v[i]->d, c->s_main);
-    if (zero_ghosts) {
-      CHECK_ARG(idx && idx[i] && idx[i]->nlids == v[i]->n, "assemble!: index set of the vector required");
-      unsigned char z[16] = {0};
-      launch_fill(dt, idx[i]->nhids, idx[i]->noids, idx[i]->d_hid_to_lid, v[i]->d, z, c->s_main);
+  for (int i = 0; i < n; ++i)
+    if (exchange_unpack(i, v, xg, idx, op, dir, pulled, zero_ghosts, xg[i]->ctx->s_main)) return -1;
+  HIPC(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Completion handles and the async exchange.
+namespace {
+
+int event_create(int device, pa_event** out) {
+  HIPC(hipSetDevice(device));
+  std::unique_ptr<pa_event> e(new pa_event());
+  e->device = device;
+  for (hipEvent_t& h : e->ev) {
+    const hipError_t rc = hipEventCreateWithFlags(&h, hipEventDisableTiming);
+    if (rc != hipSuccess) {
+      h = nullptr;
+      pa_event_destroy(e.release());
+      HIPC(rc);
     }
   }
-  HIPC(hipGetLastError());
+  *out = e.release();
+  return 0;
+}
+
+// What pa_exchange_all_async and pa_mat_exchange_all_async share.  Part i's
+// work all goes to its comm stream: the three waits (everything enqueued on
+// the context so far; after[i]; the earlier users of the exchanger buffers),
+// the pack, the transport, the unpack, tail(i, s_comm), and done[i] behind it.
+int exchange_async(int n, pa_vec* const v[], pa_xchg* const xg[], const pa_index* const idx[], int op, int dir,
+                   int zero_ghosts, pa_event* const after[], const std::function<int(int, hipStream_t)>& tail,
+                   pa_event* done[]) {
+  const int dt = v[0]->dtype;
+  for (int i = 0; i < n; ++i) done[i] = nullptr;
+  auto issue = [&]() -> int {
+    for (int i = 0; i < n; ++i)
+      if (event_create(xg[i]->ctx->device, &done[i])) return -1;
+    const LocalSet L = local_set(n, xg);
+    for (int i = 0; i < n; ++i) {
+      pa_ctx* c = xg[i]->ctx;
+      HIPC(hipSetDevice(c->device));
+      HIPC(hipEventRecord(done[i]->ev[0], c->s_main));
+      HIPC(hipStreamWaitEvent(c->s_comm, done[i]->ev[0], 0));
+      if (after && after[i])
+        for (hipEvent_t e : after[i]->ev) HIPC(hipStreamWaitEvent(c->s_comm, e, 0));
+      if (pre_pack_wait_part(i, xg, L, c->s_comm)) return -1;
+    }
+    for (int i = 0; i < n; ++i)
+      if (exchange_pack(i, v, xg, dir, xg[i]->ctx->s_comm)) return -1;
+    HIPC(hipGetLastError());
+    bool pulled = false;
+    if (transport(n, xg, dt, dir, op, v, &pulled)) return -1;
+    for (int i = 0; i < n; ++i) {
+      pa_ctx* c = xg[i]->ctx;
+      if (exchange_unpack(i, v, xg, idx, op, dir, pulled, zero_ghosts, c->s_comm)) return -1;
+      if (tail && tail(i, c->s_comm)) return -1;
+      // the unpack read the receive buffer on this stream: a later call's pack
+      // into it (pre_pack_wait_part) waits for ev_recvd, so it moves behind it
+      HIPC(hipEventRecord(c->ev_recvd, c->s_comm));
+      HIPC(hipEventRecord(done[i]->ev[1], c->s_comm));
+    }
+    HIPC(hipGetLastError());
+    return 0;
+  };
+  if (issue() == 0) return 0;
+  for (int i = 0; i < n; ++i) {  // a failed call leaves no handle behind
+    pa_event_destroy(done[i]);
+    done[i] = nullptr;
+  }
+  return -1;
+}
+
+}  // namespace
+
+int pa_exchange_all_async(int n, pa_vec* const v[], pa_xchg* const xg[], const pa_index* const idx[], int op,
+                          int reverse, int zero_ghosts, pa_event* const after[], pa_event* done[]) {
+  CHECK_ARG(done, "null done");
+  if (exchange_check(n, v, xg, op)) return -1;
+  for (int i = 0; i < n && zero_ghosts; ++i)
+    CHECK_ARG(idx && idx[i] && idx[i]->nlids == v[i]->n, "assemble!: index set of the vector required");
+  TuneScope ts(v[0]->ctx);
+  return exchange_async(n, v, xg, idx, op, reverse ? 1 : 0, zero_ghosts, after, nullptr, done);
+}
+
+int pa_mat_exchange_all_async(int n, pa_mat* const A[], pa_xchg* const xg[], int op, int reverse, int zero_sent,
+                              pa_event* const after[], pa_event* done[]) {
+  CHECK_ARG(done, "null done");
+  CHECK_ARG(n >= 1 && A && xg && A[0], "null argument");
+  std::vector<pa_vec> vs(n);
+  std::vector<pa_vec*> vp(n);
+  for (int i = 0; i < n; ++i) {
+    CHECK_ARG(A[i] && xg[i] && A[i]->ctx == xg[i]->ctx, "exchange!(A): matrix and exchanger of different parts");
+    vs[i].ctx = A[i]->ctx;
+    vs[i].dtype = A[i]->dtype;
+    vs[i].n = nvals(A[i]);
+    vs[i].d = A[i]->main.val;
+    vp[i] = &vs[i];
+  }
+  if (exchange_check(n, vp.data(), xg, op)) return -1;
+  TuneScope ts(A[0]->ctx);
+  // the sent ghost-row values zeroed and the side SELL copies refreshed, as
+  // pa_mat_exchange_all does after its exchange
+  auto tail = [&](int i, hipStream_t st) -> int {
+    if (zero_sent) {
+      unsigned char z[16] = {0};
+      const XchgSide& sent = xg[i]->from(reverse ? 1 : 0);
+      launch_fill(A[i]->dtype, sent.n, 0, sent.lids, A[i]->main.val, z, st);
+    }
+    return refresh_side(A[i], st);
+  };
+  return exchange_async(n, vp.data(), xg, nullptr, op, reverse ? 1 : 0, 0, after, tail, done);
+}
+
+int pa_event_record(pa_ctx* c, pa_event** out) {
+  CHECK_ARG(c && out, "null argument");
+  pa_event* e = nullptr;
+  if (event_create(c->device, &e)) return -1;
+  const hipStream_t st[2] = {c->s_main, c->s_comm};
+  for (int k = 0; k < 2; ++k) {
+    const hipError_t rc = hipEventRecord(e->ev[k], st[k]);
+    if (rc != hipSuccess) {
+      pa_event_destroy(e);
+      HIPC(rc);
+    }
+  }
+  *out = e;
+  return 0;
+}
+
+int pa_event_query(const pa_event* ev, int* done) {
+  CHECK_ARG(ev && done, "null argument");
+  *done = 1;
+  for (hipEvent_t e : ev->ev) {
+    const hipError_t rc = hipEventQuery(e);
+    if (rc == hipErrorNotReady) {
+      *done = 0;
+      continue;
+    }
+    HIPC(rc);
+  }
+  return 0;
+}
+
+int pa_event_wait(pa_event* ev) {
+  CHECK_ARG(ev, "null event");
+  for (hipEvent_t e : ev->ev) HIPC(hipEventSynchronize(e));
+  return 0;
+}
+
+int pa_ctx_wait_event(pa_ctx* c, const pa_event* ev) {
+  CHECK_ARG(c && ev, "null argument");
+  HIPC(hipSetDevice(c->device));
+  for (hipEvent_t e : ev->ev) HIPC(hipStreamWaitEvent(c->s_main, e, 0));
+  return 0;
+}
+
+int pa_event_destroy(pa_event* ev) {
+  if (!ev) return 0;
+  (void)hipSetDevice(ev->device);
+  for (hipEvent_t e : ev->ev)
+    if (e) (void)hipEventDestroy(e);
+  delete ev;
   return 0;
 }
 

@@ -361,6 +361,15 @@ struct pa_ctx {
   int64_t over[kMaxKnobs] = {};
 };
 
+// Completion of one call's work for one part (pa_exchange_all_async: [0] the
+// compute stream's work before the call, [1] the end of the call's work on
+// the comm stream; pa_event_record: [0] the compute stream, [1] the comm
+// stream).  The handle owns its events (no timing) on its device.
+struct pa_event {
+  int device = 0;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+};
+
 // The tuning knobs of one call (performance only, results unchanged; the
 // table with their meaning is kKnobs in pa_api.cpp).  A call resolves them
 // once — the process defaults (pa_tune) under its first part's context

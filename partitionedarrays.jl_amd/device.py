@@ -94,6 +94,46 @@ class PartContext:
             self.h = None
 
 
+class Task:
+    """pa_event: the completion of one call's work for one part, the `Task`
+    that async_exchange! / async_assemble! return per part
+    (Interfaces.jl:349-401).  A Task without a handle stands for work that
+    had completed when the call returned (the COO forms)."""
+
+    def __init__(self, ctx: PartContext, h=None):
+        self.ctx = ctx
+        self.h = h
+
+    def done(self) -> bool:
+        """pa_event_query: has the work finished?  Never blocks."""
+        if self.h is None:
+            return True
+        d = C.c_int(0)
+        _lib.call("pa_event_query", self.h, C.byref(d))
+        return d.value != 0
+
+    def wait(self):
+        """pa_event_wait: block the host on this event only"""
+        if self.h is not None:
+            _lib.call("pa_event_wait", self.h)
+        return self
+
+    def join(self, ctx: PartContext = None):
+        """pa_ctx_wait_event: what is enqueued from now on on the compute
+        stream of ctx (default: the task's own part) runs after this task;
+        the host does not wait"""
+        if self.h is not None:
+            _lib.call("pa_ctx_wait_event", (ctx or self.ctx).h, self.h)
+        return self
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None) and _lib._lib is not None and not sys.is_finalizing():
+                _lib._lib.pa_event_destroy(self.h)
+        except Exception:
+            pass
+
+
 class HIPBackend(SequentialBackend):
     """All parts in this process, part p on device devices[(p-1) % len(devices)]
     (SequentialBackend semantics, HIP parts)."""

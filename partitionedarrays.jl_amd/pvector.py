@@ -17,8 +17,8 @@ import numpy as np
 
 from . import _lib
 from .backends import PData, exchange, map_parts, unzip
-from .device import (DeviceCOO, DeviceMatrix, DeviceMatrixExchanger, DeviceVector, contexts, device_exchanger,
-                     device_index, device_index_gids)
+from .device import (DeviceCOO, DeviceMatrix, DeviceMatrixExchanger, DeviceVector, Task, contexts,
+                     device_exchanger, device_index, device_index_gids)
 from .helpers import Table, counts_to_ptrs, trace_setup
 from .prange import Exchanger, PRange, _cached_eq, empty_exchanger, hids_are_equal, oids_are_equal
 
@@ -376,6 +376,78 @@ def assemble_(v, rows: PRange = None):
     _lib.call("pa_exchange_all", len(ctxs), _hs(v.values.parts), _hs(xg), _lib.ptr_array(_idx(v)),
               _lib.PA_ADD, 1, 1)
     return v
+
+
+def _tasks(like: PData, ctxs, handles) -> PData:
+    return PData(like.backend, like.part_ids, [Task(c, h) for c, h in zip(ctxs, handles)], like.shape)
+
+
+def _async(v, rows, t0, coo_entry, op, reverse, zero):
+    """The pa_*_exchange_all_async call behind async_exchange_ and
+    async_assemble_: a PData of Tasks, one per part."""
+    if isinstance(v, COO):
+        # the COO forms size their outputs on the host: they have completed
+        # when they return
+        if rows is None:
+            raise TypeError(f"{coo_entry}: the rows PRange is required")
+        if t0 is not None:
+            wait_all(t0)
+        _coo_all(coo_entry, v, rows)
+        ctxs = contexts(v.values)
+        return _tasks(v.values, ctxs, [None] * len(ctxs))
+    ctxs = contexts(v.values)
+    n = len(ctxs)
+    if t0 is not None and t0.part_ids != v.values.part_ids:
+        raise ValueError("t0: tasks over different parts")
+    after = _hs(t0.parts) if t0 is not None else None  # the Tasks of t0 stay alive through the call
+    done = (C.c_void_p * n)()
+    if isinstance(v, PSparseMatrix):
+        _lib.call("pa_mat_exchange_all_async", n, _hs(v.values.parts), _hs(_mat_dev_xchg(v)), op, reverse, zero,
+                  after, done)
+    else:
+        xg = [device_exchanger(c, v.rows.exchanger, p) for c, p in zip(ctxs, v.values.part_ids)]
+        _lib.call("pa_exchange_all_async", n, _hs(v.values.parts), _hs(xg), _lib.ptr_array(_idx(v)), op, reverse,
+                  zero, after, done)
+    return _tasks(v.values, ctxs, [C.c_void_p(h) for h in done])
+
+
+def async_exchange_(v, t0: PData = None, rows: PRange = None) -> PData:
+    """t = async_exchange!(v) (Interfaces.jl:349-401, 2071-2075; a
+    PSparseMatrix: 2375-2381): exchange_ that returns at once with a PData of
+    Tasks.  Each part's work runs on its comm stream behind everything
+    enqueued so far on the part and behind t0 (a PData of Tasks, e.g. of
+    record or of another async call; no host wait); compute-stream work
+    enqueued afterwards does not wait for it.  From the call until
+    Task.wait() / Task.join() the values belong to the call.  A COO (with
+    rows) runs the blocking call and returns finished tasks."""
+    return _async(v, rows, t0, "pa_coo_exchange_all", _lib.PA_REPLACE, 0, 0)
+
+
+def async_assemble_(v, t0: PData = None, rows: PRange = None) -> PData:
+    """t = async_assemble!(v) (Interfaces.jl:2084-2106; a PSparseMatrix:
+    2383-2404): assemble_ as async_exchange_ runs exchange_."""
+    return _async(v, rows, t0, "pa_coo_assemble_all", _lib.PA_ADD, 1, 1)
+
+
+def wait_all(tasks: PData):
+    """wait on every task (map_parts(wait, t))"""
+    for t in tasks.parts:
+        t.wait()
+    return tasks
+
+
+def record(x) -> PData:
+    """Tasks for everything enqueued so far on the parts of x (a PVector, a
+    PSparseMatrix or a PData over the parts; pa_event_record), e.g. a mul_
+    whose result an async_exchange_ takes as t0."""
+    like = x if isinstance(x, PData) else x.values
+    ctxs = contexts(like)
+    hs = []
+    for c in ctxs:
+        h = C.c_void_p()
+        _lib.call("pa_event_record", c.h, C.byref(h))
+        hs.append(h)
+    return _tasks(like, ctxs, hs)
 
 
 def _scalar_out(dtype):
@@ -928,14 +1000,19 @@ def matrix_exchanger(values: PData, rows: PRange, cols: PRange) -> Exchanger:
     return Exchanger(parts_rcv, parts_snd, k_rcv, k_snd)
 
 
-def _mat_exchange(A: "PSparseMatrix", op, reverse, zero_sent):
+def _mat_dev_xchg(A: "PSparseMatrix"):
+    """the device exchangers over nonzeros(A), created on first use"""
     if A._dev_xchg is None:
         ex = A.exchanger
         A._dev_xchg = [DeviceMatrixExchanger(M, ex.parts_rcv.local(p), ex.lids_rcv.local(p),
                                              ex.parts_snd.local(p), ex.lids_snd.local(p))
                        for M, p in zip(A.values.parts, A.values.part_ids)]
-    _lib.call("pa_mat_exchange_all", len(A._dev_xchg), _hs(A.values.parts), _hs(A._dev_xchg), op, reverse,
-              zero_sent)
+    return A._dev_xchg
+
+
+def _mat_exchange(A: "PSparseMatrix", op, reverse, zero_sent):
+    xg = _mat_dev_xchg(A)
+    _lib.call("pa_mat_exchange_all", len(xg), _hs(A.values.parts), _hs(xg), op, reverse, zero_sent)
     return A
 
 
