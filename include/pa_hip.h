@@ -131,6 +131,9 @@ int pa_device_count(int* count);
  *               their values at slice * H * |U| in U's order, so the
  *               short-row tail launch issues its loads before the slice's
  *               descriptor arrives (matrices built afterwards); 0 off;
+ * "scatter_wide" 0 (default): pa_vec_scatter sorts 32-bit keys and payloads
+ *               when the part's lids and the entries fit them, 1: always the
+ *               64-bit ones;
  * "fault_inject" tests only: threaded issue jobs add an invalid launch. */
 int pa_tune(const char* key, int value, int* previous);
 /* The same knobs for one context: calls led by parts of `c` (their first
@@ -281,6 +284,48 @@ int pa_vec_copy(pa_vec* dst, const pa_index* idx_dst,
 #define PA_BCAST_C128 16
 int pa_vec_axpby(pa_vec* y, const pa_vec* x, const pa_index* idx,
                  const void* a, int mode, int all_lids);
+
+/* ---- COO constructor and indexed views of a PVector ----------------------
+ * pa_vec_scatter: the n pairs (I[k], V[k]) written into the values of one
+ * part, in input order.  With op PA_SCATTER_ADD and zero_first = 1 it is the
+ * loop of PVector(init, I, V, rows; ids) (Interfaces.jl:1887-1910): the
+ * values are filled with zero(T) over all lids (1901), then
+ * values[lid] += V[k] for k = 1..n (1902-1905) — a single -0.0 entry gives
+ * +0.0; with zero_first = 0 it is the batched `view[I] .+= V` on
+ * local_view / global_view (test_fem_sa.jl:86-101), and op PA_SCATTER_SET
+ * their setindex! (2027-2031, 2066-2069): the last entry of an id in input
+ * order stays.  The result equals the sequential loop bit for bit whatever
+ * the duplicates: the pairs are sorted stably by lid and each lid's entries
+ * are added to it in input order by one thread, with plain adds (complex
+ * values componentwise), no atomics.
+ * ids_kind PA_IDS_LOCAL: I holds 1-based lids of idx (index_bytes 4 or 8); an
+ * id outside 1..num_lids is an error (BoundsError).  PA_IDS_GLOBAL: I holds
+ * 1-based Int64 gids (index_bytes 8), looked up in the gid table of idx
+ * (pa_index_set_gids) and overwritten in place by the 1-based lids, as
+ * to_lids! does in the constructor (1886, 1895-1897; visible in the sequence
+ * test_interfaces.jl:501-503); a gid that is not a local id is an error
+ * (KeyError).  Every id is checked before the first write: a failed call
+ * leaves v and I unchanged.  idx must be the index set of v (num_lids = the
+ * vector's length).  n = 0 and parts without lids are legal.
+ * on_device = 1: I and V (pa_vec_gather: I and out) are device arrays on the
+ * context's device — a ROCArray of the Julia caller, next to
+ * pa_vec_device_ptr; otherwise host arrays, consumed before the call
+ * returns.  The work is enqueued on the part's compute stream, ordered with
+ * the part's other work.
+ * pa_vec_gather: out[k] = v[lid of I[k]], getindex of the views.  An absent
+ * global id reads zero(T) when absent_zero = 1 (LocalView, 2019-2026) and is
+ * an error (KeyError) when 0 (GlobalView, 2062-2065); a local id out of range
+ * is always an error.  I is left unchanged.                                 */
+#define PA_IDS_LOCAL 0   /* 1-based lids of idx */
+#define PA_IDS_GLOBAL 1  /* 1-based Int64 gids; needs pa_index_set_gids */
+#define PA_SCATTER_ADD 0
+#define PA_SCATTER_SET 1
+int pa_vec_scatter(pa_vec* v, pa_index* idx, int ids_kind, int index_bytes,
+                   int op, int zero_first, int on_device,
+                   int64_t n, void* I, const void* V);
+int pa_vec_gather(const pa_vec* v, pa_index* idx, int ids_kind, int index_bytes,
+                  int absent_zero, int on_device,
+                  int64_t n, const void* I, void* out);
 
 /* ---- broadcast expressions (Interfaces.jl:1688-1765) --------------------
  * Any elementwise expression over PVectors and numbers as one pass: a

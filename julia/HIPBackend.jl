@@ -20,7 +20,10 @@
 #     broadcast, the Euclidean distances (1682-1686, 1774-1863),
 #     IterativeSolvers.cg! (v0.9, test_fdm.jl:115), and the COO triplet
 #     exchanges assemble!(I, J, V, rows) (2406-2492) and
-#     exchange!(I, J, V, rows) (2494-2592);
+#     exchange!(I, J, V, rows) (2494-2592), the COO constructor
+#     PVector(init, I, V, rows; ids) (1887-1932) and batched reads and writes
+#     through global / local ids (view_add!, view_set!, view_get: the
+#     global_view / local_view access of 1994-2069 without a download);
 #   * everything else (PRange, Exchanger, add_gids!, gather/scatter setup
 #     collectives) runs unchanged on the host parts.
 #
@@ -659,6 +662,108 @@ function async_exchange!(I::HIPData{<:Vector{<:Integer}}, J::HIPData{<:Vector{<:
                          t0::AbstractPData=PartitionedArrays._empty_tasks(rows.exchanger.parts_rcv)) where {T<:DeviceEltype}
   _wait_all(t0)
   _coo_all!(true, I, J, V, rows)
+end
+
+# ---- PVector(init, I, V, rows; ids) and the indexed views -------------------
+# The COO constructor (Interfaces.jl:1887-1910) and the batched forms of
+# `view[I] .+= V`, `view[I] = V` and `view[I]` over global_view / local_view
+# (1994-2069) as one ordered scatter / gather per part (pa_vec_scatter,
+# pa_vec_gather): values[lid] += V[i] in input order, bit for bit the
+# reference's loop.  PVector(init, I, V, n; ids) (1920-1932) reaches the
+# constructor below through the reference's own method (PRange, add_gids!).
+const PA_IDS_LOCAL, PA_IDS_GLOBAL = Cint(0), Cint(1)
+const PA_SCATTER_ADD, PA_SCATTER_SET = Cint(0), Cint(1)
+_ids_kind(ids::Symbol) = ids === :global ? PA_IDS_GLOBAL : PA_IDS_LOCAL
+# the ids as the library takes them: Int64 gids, Int32 or Int64 lids (a copy
+# unless they already are such a Vector; gids are translated in it)
+_ids_vector(I::Vector{Int64}, ids::Symbol) = I
+_ids_vector(I::Vector{Int32}, ids::Symbol) = ids === :global ? Int64.(I) : I
+_ids_vector(I::AbstractArray{<:Integer}, ids::Symbol) = Int64.(collect(I))
+
+function _vec_scatter!(h::Ptr{Cvoid}, ih::Ptr{Cvoid}, ids::Symbol, op::Cint, zero_first::Bool,
+                       I::Vector{Ti}, V::Vector{T}) where {Ti<:Union{Int32,Int64},T<:DeviceEltype}
+  @assert length(I) == length(V)
+  check(ccall((:pa_vec_scatter, libpa), Cint,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Int64, Ptr{Ti}, Ptr{T}),
+              h, ih, _ids_kind(ids), Cint(sizeof(Ti)), op, Cint(zero_first), Cint(0), length(I), I, V))
+end
+function _vec_gather(h::Ptr{Cvoid}, ih::Ptr{Cvoid}, ids::Symbol, absent_zero::Bool,
+                     I::Vector{Ti}, ::Type{T}) where {Ti<:Union{Int32,Int64},T<:DeviceEltype}
+  out = Vector{T}(undef, length(I))
+  check(ccall((:pa_vec_gather, libpa), Cint,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Cint, Cint, Int64, Ptr{Ti}, Ptr{T}),
+              h, ih, _ids_kind(ids), Cint(sizeof(Ti)), Cint(absent_zero), Cint(0), length(I), I, out))
+  out
+end
+# the same over device arrays of the caller (a ROCArray's pointer, next to
+# pa_vec_device_ptr): on_device = 1, ids of index_bytes bytes each
+function _vec_scatter_dev!(h::Ptr{Cvoid}, ih::Ptr{Cvoid}, ids::Symbol, op::Cint, zero_first::Bool,
+                           index_bytes::Integer, n::Integer, dI::Ptr{Cvoid}, dV::Ptr{Cvoid})
+  check(ccall((:pa_vec_scatter, libpa), Cint,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
+              h, ih, _ids_kind(ids), Cint(index_bytes), op, Cint(zero_first), Cint(1), n, dI, dV))
+end
+function _vec_gather_dev!(h::Ptr{Cvoid}, ih::Ptr{Cvoid}, ids::Symbol, absent_zero::Bool,
+                          index_bytes::Integer, n::Integer, dI::Ptr{Cvoid}, dout::Ptr{Cvoid})
+  check(ccall((:pa_vec_gather, libpa), Cint,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Cint, Cint, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
+              h, ih, _ids_kind(ids), Cint(index_bytes), Cint(absent_zero), Cint(1), n, dI, dout))
+end
+
+_view_idx(a::PVector, ids::Symbol) =
+  [(ids === :global ? _idx_gids_handle : _idx_handle)(a.rows.partition.ctxs[i], a.rows.partition.parts[i])
+   for i in eachindex(a.rows.partition.parts)]
+
+# op over every part; with ids = :global the Int64 vectors of I hold lids afterwards
+function _scatter_parts!(a::HIPVector{T}, hs, I::HIPData, V::HIPData, ids::Symbol, op::Cint,
+                         zero_first::Bool, translate::Bool) where {T<:DeviceEltype}
+  @assert ids in (:global, :local)
+  ih = _view_idx(a, ids)
+  for i in eachindex(a.values.parts)
+    Ii = _ids_vector(I.parts[i], ids)
+    ids === :global && !translate && Ii === I.parts[i] && (Ii = copy(Ii))
+    _vec_scatter!(hs[i], ih[i], ids, op, zero_first, Ii, convert(Vector{T}, V.parts[i]))
+    ids === :global && translate && Ii !== I.parts[i] && (I.parts[i] .= Ii)
+  end
+  mark_device_newer!(a)
+end
+
+function PVector(init, I::HIPData{<:AbstractArray{<:Integer}}, V::HIPData{<:AbstractArray},
+                 rows::PRange; ids::Symbol)
+  @assert ids in (:global, :local)
+  values = map_parts(partition -> init(num_lids(partition)), rows.partition)
+  a = PVector(values, rows)
+  if !(eltype(a) <: DeviceEltype)   # e.g. the Int vectors of test_interfaces.jl: the host loop
+    ids === :global && PartitionedArrays.to_lids!(I, rows)
+    map_parts(values, I, V) do values, I, V
+      fill!(values, zero(eltype(values)))
+      for i in 1:length(I)
+        values[I[i]] += V[i]
+      end
+    end
+    return a
+  end
+  # fill!(values, zero(T)) and the loop on the device; I is translated in
+  # place for ids = :global, as to_lids! does in the reference (1895-1897)
+  _scatter_parts!(a, dev_vec_nocopy(a), I, V, ids, PA_SCATTER_ADD, true, true)
+end
+
+"""`view[I[k]] += V[k]` for every k in input order, over `global_view(a, a.rows)`
+(ids = :global) or `local_view(a, a.rows)` (ids = :local), per part, on the device."""
+view_add!(a::HIPVector, I::HIPData, V::HIPData; ids::Symbol) =
+  _scatter_parts!(a, dev_vec(a), I, V, ids, PA_SCATTER_ADD, false, false)
+"""`view[I[k]] = V[k]` in input order (a repeated id keeps its last value)."""
+view_set!(a::HIPVector, I::HIPData, V::HIPData; ids::Symbol) =
+  _scatter_parts!(a, dev_vec(a), I, V, ids, PA_SCATTER_SET, false, false)
+"""`view[I]` per part.  A gid that is not a local id reads zero(T) with
+absent_zero (LocalView, Interfaces.jl:2019-2026) and is an error without
+(GlobalView, 2062-2065)."""
+function view_get(a::HIPVector{T}, I::HIPData; ids::Symbol, absent_zero::Bool=false) where {T<:DeviceEltype}
+  @assert ids in (:global, :local)
+  hs, ih = dev_vec(a), _view_idx(a, ids)
+  out = [_vec_gather(hs[i], ih[i], ids, absent_zero, _ids_vector(I.parts[i], ids), T)
+         for i in eachindex(a.values.parts)]
+  HIPData(out, a.values.ctxs, a.values.backend)
 end
 
 # ---- reductions (Interfaces.jl:221-238, 1767-1772, 1973-1992) -------------

@@ -19,6 +19,8 @@ PA_F32, PA_F64, PA_C64, PA_C128 = 0, 1, 2, 3
 PA_REPLACE, PA_ADD = 0, 1
 TUNE_DROP = -(2 ** 31)  # pa_ctx_tune: drop a context's override (PA_TUNE_DROP)
 PA_BCAST_F64, PA_BCAST_C128 = 8, 16  # pa_vec_axpby scalar kinds (Float64 / ComplexF64 scalars)
+PA_IDS_LOCAL, PA_IDS_GLOBAL = 0, 1  # pa_vec_scatter / pa_vec_gather: 1-based lids, or Int64 gids
+PA_SCATTER_ADD, PA_SCATTER_SET = 0, 1
 
 # broadcast expressions (pa_expr of include/pa_hip.h)
 EXPR_MAX_OPS, EXPR_MAX_VECS, EXPR_MAX_SCALARS, EXPR_MAX_DEPTH = 32, 8, 8, 4
@@ -85,6 +87,8 @@ _SIGS = {
     "pa_vec_fill": [_p, _p],
     "pa_vec_copy": [_p, _p, _p, _p, C.c_int],
     "pa_vec_axpby": [_p, _p, _p, _p, C.c_int, C.c_int],
+    "pa_vec_scatter": [_p, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, _p, _p],
+    "pa_vec_gather": [_p, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, _p, _p],
     "pa_expr_check": [_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "pa_vec_eval": [_p, _p, _p, C.c_int, C.POINTER(_p), C.POINTER(_p), C.c_int, _p, C.POINTER(C.c_int), C.c_int],
     "pa_reduce_expr_all": [C.c_int, C.c_int, _p, C.c_int, C.POINTER(_p), C.POINTER(_p), C.c_int, _p,

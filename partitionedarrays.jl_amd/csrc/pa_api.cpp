@@ -84,12 +84,14 @@ void launch_gather_scatter(int P, const void* const* srcs, int accsz, int nd, vo
 //    1.075 ms (profiles/r03/s, final, f, d) — the fused SpMV gathers two
 //    vectors (r and u_old) per x value — so 2 = measure one batch of each on
 //    this box and keep the faster (pa_cg_solve_all);
+//  * scatter_wide 0: the ordered vector scatter sorts 32-bit keys when they fit;
 //  * spmv_flags 223, spmv_format 1, long_rows_exact 1: pa_spmv.hip.
 const Knobs kDefaults = {
     /*spmv_flags*/ 223, /*long_exact*/ 1, /*halo_pull*/ 1, /*spmv_delta16*/ 1, /*spmv_merge*/ 1,
     /*spmv_merge_max*/ 65536, /*cg_fuse*/ 2, /*halo_direct*/ 1, /*halo_transport*/ 0, /*spmv_group*/ 1,
     /*spmv_format*/ 1, /*pattern_min_pct*/ 0, /*issue_threads*/ 1, /*fault_inject*/ 0, /*spmv_xcd_chunk*/ -1, /*spmv_tri16*/ 1,
-    /*halo_barrier*/ 1, /*tri_order*/ 1, /*side_tail*/ 1, /*f32_rows*/ 0, /*tri_pack*/ 7, /*uniform*/ 1};
+    /*halo_barrier*/ 1, /*tri_order*/ 1, /*side_tail*/ 1, /*f32_rows*/ 0, /*tri_pack*/ 7, /*uniform*/ 1,
+    /*scatter_wide*/ 0};
 // COO → CSC → SELL on the device (pa_coo.hip)
 int coo_compress(int dtype, int index_bytes, int64_t m, int64_t ncols, int64_t n, const void* dI, const void* dJ,
                  const void* dV, int csr, int64_t* nu_out, DevBuf<int32_t>& crow, DevBuf<int32_t>& ccol,
@@ -1489,6 +1491,9 @@ const Knob kKnobs[] = {
      "launches (big single parts) take C = the pattern's reach in blocks / 8, so that a block's z-neighbour "
      "plane runs on its XCD (FE27 256^3 F64: C = 16, -1.0..-1.2 %, profiles/r05/q,r/), merged launches keep "
      "the round robin (C2: C = 4 +1.4 %, r05/k/)"},
+    {"scatter_wide", &Knobs::scatter_wide, nullptr, 0, 1, 0,
+     "scatter_wide: the ordered vector scatter (pa_vec_scatter) sorts 0 = 32-bit keys and payloads when the "
+     "part's local ids and the entries fit them (default), 1 = always the 64-bit ones (A/B, tests)"},
     {"fault_inject", &Knobs::fault_inject, nullptr, 0, 1, 0,
      "fault_inject: 1 = every job of a threaded issue (IssuePool) also issues an invalid kernel launch (tests "
      "of the error path; test_exception.jl's role), 0 = off (default)"},
@@ -2240,6 +2245,87 @@ int pa_vec_axpby(pa_vec* y, const pa_vec* x, const pa_index* idx, const void* a,
     launch_axpby(y->dtype, idx->noids, idx->d_oid_to_lid, y->d, x ? x->d : nullptr, a, mode, y->ctx->s_main, sk);
   }
   HIPC(hipGetLastError());
+  return 0;
+}
+
+// the argument checks pa_vec_scatter and pa_vec_gather share (no device
+// needed; the scalar arguments first, so that they are reported whatever the
+// handles are)
+static int vec_ids_check(const char* who, const pa_vec* v, const pa_index* idx, int ids_kind, int index_bytes,
+                         int64_t n, const void* I, const void* vals) {
+  const std::string w = std::string(who) + ": ";
+  CHECK_ARG(ids_kind == PA_IDS_LOCAL || ids_kind == PA_IDS_GLOBAL, w + "ids_kind must be PA_IDS_LOCAL or PA_IDS_GLOBAL");
+  CHECK_ARG(index_bytes == 4 || index_bytes == 8, w + "index_bytes must be 4 or 8");
+  CHECK_ARG(ids_kind != PA_IDS_GLOBAL || index_bytes == 8, w + "ids=:global needs Int64 ids (index_bytes 8)");
+  CHECK_ARG(n >= 0, w + "negative length");
+  CHECK_ARG(v && idx && (n == 0 || (I && vals)), w + "null argument");
+  CHECK_ARG(v->ctx == idx->ctx, w + "the vector and the index set belong to different parts");
+  CHECK_ARG(v->n == idx->nlids, w + "the index set does not have the vector's local ids");
+  CHECK_ARG(ids_kind != PA_IDS_GLOBAL || idx->has_gids, w + "call pa_index_set_gids first");
+  return 0;
+}
+
+// a device array of `bytes` bytes for a call's input: the caller's own
+// (on_device) or a copy of the host array in `own`, enqueued on st
+static int vec_stage(int on_device, const void* p, size_t bytes, DevBuf<void>& own, hipStream_t st, void** dev) {
+  *dev = const_cast<void*>(p);
+  if (on_device || bytes == 0) return 0;
+  HIPC(own.alloc(bytes));
+  HIPC(hipMemcpyAsync(own, p, bytes, hipMemcpyHostToDevice, st));
+  *dev = own.p;
+  return 0;
+}
+
+int pa_vec_scatter(pa_vec* v, pa_index* idx, int ids_kind, int index_bytes, int op, int zero_first, int on_device,
+                   int64_t n, void* I, const void* V) {
+  CHECK_ARG(op == PA_SCATTER_ADD || op == PA_SCATTER_SET, "pa_vec_scatter: op must be PA_SCATTER_ADD or PA_SCATTER_SET");
+  if (vec_ids_check("pa_vec_scatter", v, idx, ids_kind, index_bytes, n, I, V)) return -1;
+  pa_ctx* c = v->ctx;
+  TuneScope ts(c);
+  HIPC(hipSetDevice(c->device));
+  const bool global = ids_kind == PA_IDS_GLOBAL;
+  const size_t ibytes = (size_t)n * index_bytes;
+  DevBuf<void> bI, bV;
+  void *dI = nullptr, *dV = nullptr;
+  if (vec_stage(on_device, I, ibytes, bI, c->s_main, &dI) ||
+      vec_stage(on_device, V, (size_t)n * dtype_size(v->dtype), bV, c->s_main, &dV))
+    return -1;
+  const bool wide = knobs().scatter_wide || (uint64_t)v->n > (1ull << 32) || (uint64_t)n > (1ull << 32);
+  const int rc = vec_scatter(v->dtype, v->n, v->d, global, index_bytes, op == PA_SCATTER_SET, zero_first != 0, wide, n,
+                             dI, dV, idx->d_sgid, idx->d_slid, c->s_main);
+  CHECK_ARG(rc >= 0, "pa_vec_scatter: device pass failed");
+  if (rc && global) PA_FAIL("to_lids!: a global id is not a local id of the part (KeyError)");
+  if (rc) PA_FAIL("pa_vec_scatter: a local id is out of range (BoundsError)");
+  if (global && !on_device && n > 0) {  // the caller's I holds the lids now
+    HIPC(hipMemcpyAsync(I, dI, ibytes, hipMemcpyDeviceToHost, c->s_main));
+    HIPC(hipStreamSynchronize(c->s_main));
+  }
+  return 0;
+}
+
+int pa_vec_gather(const pa_vec* v, pa_index* idx, int ids_kind, int index_bytes, int absent_zero, int on_device,
+                  int64_t n, const void* I, void* out) {
+  if (vec_ids_check("pa_vec_gather", v, idx, ids_kind, index_bytes, n, I, out)) return -1;
+  pa_ctx* c = v->ctx;
+  HIPC(hipSetDevice(c->device));
+  const bool global = ids_kind == PA_IDS_GLOBAL;
+  const size_t obytes = (size_t)n * dtype_size(v->dtype);
+  DevBuf<void> bI, bO;
+  void *dI = nullptr, *dO = out;
+  if (vec_stage(on_device, I, (size_t)n * index_bytes, bI, c->s_main, &dI)) return -1;
+  if (!on_device && n > 0) {
+    HIPC(bO.alloc(obytes));
+    dO = bO.p;
+  }
+  const int rc = vec_gather(v->dtype, v->n, v->d, global, index_bytes, absent_zero != 0, n, dI, dO, idx->d_sgid,
+                            idx->d_slid, c->s_main);
+  CHECK_ARG(rc >= 0, "pa_vec_gather: device pass failed");
+  if (rc && global) PA_FAIL("pa_vec_gather: a global id is not a local id of the part (KeyError)");
+  if (rc) PA_FAIL("pa_vec_gather: a local id is out of range (BoundsError)");
+  if (!on_device && n > 0) {
+    HIPC(hipMemcpyAsync(out, dO, obytes, hipMemcpyDeviceToHost, c->s_main));
+    HIPC(hipStreamSynchronize(c->s_main));
+  }
   return 0;
 }
 

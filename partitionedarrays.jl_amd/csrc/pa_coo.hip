@@ -201,17 +201,19 @@ inline int bits_for(uint64_t maxkey) {
   return b;
 }
 
-// stable sort of (key, idx) pairs in place (double buffer + temp storage)
-hipError_t sort_pairs(DevBuf<uint64_t>& key, DevBuf<int64_t>& idx, int64_t n, int end_bit, hipStream_t st) {
+// stable sort of (key, idx) pairs in place (double buffer + temp storage);
+// 64-bit keys and payloads, or 32-bit ones (the ordered vector scatter)
+template <typename K, typename P>
+hipError_t sort_pairs(DevBuf<K>& key, DevBuf<P>& idx, int64_t n, int end_bit, hipStream_t st) {
   if (n <= 1) return hipSuccess;
-  DevBuf<uint64_t> k2;
-  DevBuf<int64_t> i2;
+  DevBuf<K> k2;
+  DevBuf<P> i2;
   DevBuf<void> tmp;
   size_t tb = 0;
   hipError_t e = k2.alloc(n);
   if (e == hipSuccess) e = i2.alloc(n);
-  rocprim::double_buffer<uint64_t> kb(key.p, k2.p);
-  rocprim::double_buffer<int64_t> ib(idx.p, i2.p);
+  rocprim::double_buffer<K> kb(key.p, k2.p);
+  rocprim::double_buffer<P> ib(idx.p, i2.p);
   if (e == hipSuccess) e = rocprim::radix_sort_pairs(nullptr, tb, kb, ib, (size_t)n, 0, (unsigned)end_bit, st);
   if (e == hipSuccess) e = tmp.alloc(tb ? tb : 1);
   if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp.p, tb, kb, ib, (size_t)n, 0, (unsigned)end_bit, st);
@@ -756,6 +758,196 @@ int coo_send_pack(bool to_ghosts, int dtype, const CooList& in, const uint64_t* 
   PA_HIP_OR(hipStreamSynchronize(st), -1);
   if (hbad) return hbad;  // 1: unknown gid, 2: ghost row without a segment (assemble! only)
   return coo_pack_by_key(dtype, in, key, idx, nseg, !to_ghosts, out, cnt, st) == hipSuccess ? 0 : -1;
+}
+
+// ---------------------------------------------------------------------------
+// PVector(I, V, rows; ids) (Interfaces.jl:1887-1932) and the writes and reads
+// of local_view / global_view (1994-2069) on the device: an ordered scatter
+// of n pairs (id, V) into one part's values, and its gather twin.  The
+// reference's loop `values[lid] += V[i]` runs in input order; here the pairs
+// are sorted stably by lid (input position as payload) and the thread at the
+// first entry of each distinct lid folds that lid's entries in input order
+// with plain adds, so the result equals the loop's bit for bit whatever the
+// duplicates, without atomics.
+
+// the 0-based lid of a 1-based id, or -1: a local id out of 1..nl
+// (BoundsError), a global id absent from the gid table (KeyError)
+template <bool GLOBAL, typename IT>
+__device__ inline int64_t vec_lid(IT id, const uint64_t* __restrict__ sgid, const int64_t* __restrict__ slid,
+                                  int64_t nl) {
+  if (GLOBAL) return gid_lookup((int64_t)id, sgid, slid, nl);
+  const int64_t l = (int64_t)id - 1;
+  return (l < 0 || l >= nl) ? -1 : l;
+}
+
+// key[k] = the lid of id k, pay[k] = k; *bad = 1 when an id has no lid
+template <bool GLOBAL, typename IT, typename K, typename P>
+__global__ void k_vec_keys(int64_t n, const IT* __restrict__ I, const uint64_t* __restrict__ sgid,
+                           const int64_t* __restrict__ slid, int64_t nl, K* __restrict__ key, P* __restrict__ pay,
+                           int* __restrict__ bad) {
+  for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t l = vec_lid<GLOBAL>(I[k], sgid, slid, nl);
+    if (l < 0) *bad = 1;
+    key[k] = l < 0 ? (K)0 : (K)l;
+    pay[k] = (P)k;
+  }
+}
+
+// to_lids!: the ids become 1-based lids (before the sort, key is in input order)
+template <typename K>
+__global__ void k_vec_lids_out(int64_t n, const K* __restrict__ key, int64_t* __restrict__ I) {
+  for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x)
+    I[k] = (int64_t)key[k] + 1;
+}
+
+// key sorted (stable), pay the input positions.  The thread at the first
+// entry of a lid owns it: add: acc = v[lid]; acc = acc + V[..] over the lid's
+// entries in input order; set: the last entry in input order.  Every key is
+// below nl (k_vec_keys, checked by the caller before this pass).
+template <typename T, typename K, typename P, bool SET>
+__global__ void k_vec_scatter(int64_t n, const K* __restrict__ key, const P* __restrict__ pay,
+                              const T* __restrict__ V, T* __restrict__ v) {
+  for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
+    const K l = key[k];
+    if (k > 0 && key[k - 1] == l) continue;
+    int64_t e = k + 1;
+    if (SET) {
+      while (e < n && key[e] == l) ++e;
+      v[l] = V[pay[e - 1]];
+    } else {
+      T acc = v[l];
+      acc = acc + V[pay[k]];
+      for (; e < n && key[e] == l; ++e) acc = acc + V[pay[e]];
+      v[l] = acc;
+    }
+  }
+}
+
+// out[k] = v[lid(id k)]; an id without a lid reads zero(T), and sets *bad
+// unless it is an absent global id that may read as zero (LocalView, 2019-2026)
+template <typename T, bool GLOBAL, typename IT>
+__global__ void k_vec_gather(int64_t n, const IT* __restrict__ I, const uint64_t* __restrict__ sgid,
+                             const int64_t* __restrict__ slid, int64_t nl, const T* __restrict__ v,
+                             T* __restrict__ out, int absent_zero, int* __restrict__ bad) {
+  for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t l = vec_lid<GLOBAL>(I[k], sgid, slid, nl);
+    if (l < 0 && !(GLOBAL && absent_zero)) *bad = 1;
+    out[k] = l < 0 ? zero_of<T>() : v[l];
+  }
+}
+
+namespace {
+
+template <typename K, typename P>
+void vec_keys(bool global, int index_bytes, int64_t n, const void* I, const uint64_t* sgid, const int64_t* slid,
+              int64_t nl, K* key, P* pay, int* bad, hipStream_t st) {
+  if (global)
+    hipLaunchKernelGGL((k_vec_keys<true, int64_t, K, P>), grid1(n), dim3(256), 0, st, n, (const int64_t*)I, sgid,
+                       slid, nl, key, pay, bad);
+  else if (index_bytes == 8)
+    hipLaunchKernelGGL((k_vec_keys<false, int64_t, K, P>), grid1(n), dim3(256), 0, st, n, (const int64_t*)I, sgid,
+                       slid, nl, key, pay, bad);
+  else
+    hipLaunchKernelGGL((k_vec_keys<false, int32_t, K, P>), grid1(n), dim3(256), 0, st, n, (const int32_t*)I, sgid,
+                       slid, nl, key, pay, bad);
+}
+
+template <typename T, typename K, typename P>
+void vec_scatter_t(bool set, int64_t n, const K* key, const P* pay, const void* V, void* v, hipStream_t st) {
+  if (set)
+    hipLaunchKernelGGL((k_vec_scatter<T, K, P, true>), grid1(n), dim3(256), 0, st, n, key, pay, (const T*)V, (T*)v);
+  else
+    hipLaunchKernelGGL((k_vec_scatter<T, K, P, false>), grid1(n), dim3(256), 0, st, n, key, pay, (const T*)V, (T*)v);
+}
+
+// the scatter with keys of type K and payloads of type P (n >= 1)
+template <typename K, typename P>
+int vec_scatter_kp(int dtype, int64_t nl, void* v, bool global, int index_bytes, bool set, bool zero_first,
+                   int64_t n, void* I, const void* V, const uint64_t* sgid, const int64_t* slid, hipStream_t st) {
+  DevBuf<K> key;
+  DevBuf<P> pay;
+  DevBuf<int> bad;
+  int hbad = 0;
+  PA_HIP_OR(key.alloc(n), -1);
+  PA_HIP_OR(pay.alloc(n), -1);
+  PA_HIP_OR(bad.alloc(1), -1);
+  PA_HIP_OR(hipMemsetAsync(bad, 0, sizeof(int), st), -1);
+  vec_keys<K, P>(global, index_bytes, n, I, sgid, slid, nl, key.p, pay.p, bad.p, st);
+  PA_HIP_OR(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, st), -1);
+  PA_HIP_OR(hipStreamSynchronize(st), -1);
+  if (hbad) return 1;  // nothing written so far
+  if (global) hipLaunchKernelGGL(k_vec_lids_out<K>, grid1(n), dim3(256), 0, st, n, key.p, (int64_t*)I);
+  if (zero_first) PA_HIP_OR(hipMemsetAsync(v, 0, (size_t)nl * dtype_size(dtype), st), -1);
+  PA_HIP_OR(sort_pairs(key, pay, n, bits_for((uint64_t)(nl - 1)), st), -1);
+  switch (dtype) {
+    case PA_F32: vec_scatter_t<float, K, P>(set, n, key, pay, V, v, st); break;
+    case PA_F64: vec_scatter_t<double, K, P>(set, n, key, pay, V, v, st); break;
+    case PA_C64: vec_scatter_t<c64, K, P>(set, n, key, pay, V, v, st); break;
+    case PA_C128: vec_scatter_t<c128, K, P>(set, n, key, pay, V, v, st); break;
+  }
+  PA_HIP_OR(hipGetLastError(), -1);
+  PA_HIP_OR(hipStreamSynchronize(st), -1);  // key, pay and the caller's copies of I, V are freed on return
+  return 0;
+}
+
+template <typename T>
+void vec_gather_t(bool global, int index_bytes, int64_t n, const void* I, const uint64_t* sgid, const int64_t* slid,
+                  int64_t nl, const void* v, void* out, int absent_zero, int* bad, hipStream_t st) {
+  if (global)
+    hipLaunchKernelGGL((k_vec_gather<T, true, int64_t>), grid1(n), dim3(256), 0, st, n, (const int64_t*)I, sgid,
+                       slid, nl, (const T*)v, (T*)out, absent_zero, bad);
+  else if (index_bytes == 8)
+    hipLaunchKernelGGL((k_vec_gather<T, false, int64_t>), grid1(n), dim3(256), 0, st, n, (const int64_t*)I, sgid,
+                       slid, nl, (const T*)v, (T*)out, absent_zero, bad);
+  else
+    hipLaunchKernelGGL((k_vec_gather<T, false, int32_t>), grid1(n), dim3(256), 0, st, n, (const int32_t*)I, sgid,
+                       slid, nl, (const T*)v, (T*)out, absent_zero, bad);
+}
+
+}  // namespace
+
+// One part's ordered scatter: v (nl values of dtype) takes the n pairs
+// (I[k], V[k]) — I: 1-based lids (index_bytes 4 or 8) or, global, 1-based
+// Int64 gids looked up in (sgid, slid) and overwritten by their 1-based lids;
+// set: the last entry of a lid in input order is stored, else the entries are
+// added to v[lid] in input order, from zero(T) everywhere when zero_first.
+// I, V: device arrays.  wide: 64-bit sort keys and payloads (needed when nl
+// or n exceeds 32 bits).  Returns 1 when an id has no lid (v and I are then
+// unchanged), -1 on a HIP error.  The work is complete on return.
+int vec_scatter(int dtype, int64_t nl, void* v, bool global, int index_bytes, bool set, bool zero_first, bool wide,
+                int64_t n, void* I, const void* V, const uint64_t* sgid, const int64_t* slid, hipStream_t st) {
+  if (n <= 0) {
+    if (zero_first && nl > 0) PA_HIP_OR(hipMemsetAsync(v, 0, (size_t)nl * dtype_size(dtype), st), -1);
+    return 0;
+  }
+  if (nl <= 0) return 1;  // no id has a lid
+  if (wide) return vec_scatter_kp<uint64_t, int64_t>(dtype, nl, v, global, index_bytes, set, zero_first, n, I, V,
+                                                     sgid, slid, st);
+  return vec_scatter_kp<uint32_t, uint32_t>(dtype, nl, v, global, index_bytes, set, zero_first, n, I, V, sgid, slid,
+                                            st);
+}
+
+// One part's gather: out[k] = v[lid of I[k]] (I, out: device arrays, n
+// entries).  absent_zero: an absent global id reads zero(T); otherwise, and
+// for a local id out of range, the call returns 1 (out is then unspecified).
+// -1 on a HIP error.  The work is complete on return.
+int vec_gather(int dtype, int64_t nl, const void* v, bool global, int index_bytes, bool absent_zero, int64_t n,
+               const void* I, void* out, const uint64_t* sgid, const int64_t* slid, hipStream_t st) {
+  if (n <= 0) return 0;
+  DevBuf<int> bad;
+  int hbad = 0;
+  PA_HIP_OR(bad.alloc(1), -1);
+  PA_HIP_OR(hipMemsetAsync(bad, 0, sizeof(int), st), -1);
+  switch (dtype) {
+    case PA_F32: vec_gather_t<float>(global, index_bytes, n, I, sgid, slid, nl, v, out, absent_zero, bad, st); break;
+    case PA_F64: vec_gather_t<double>(global, index_bytes, n, I, sgid, slid, nl, v, out, absent_zero, bad, st); break;
+    case PA_C64: vec_gather_t<c64>(global, index_bytes, n, I, sgid, slid, nl, v, out, absent_zero, bad, st); break;
+    case PA_C128: vec_gather_t<c128>(global, index_bytes, n, I, sgid, slid, nl, v, out, absent_zero, bad, st); break;
+  }
+  PA_HIP_OR(hipGetLastError(), -1);
+  PA_HIP_OR(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, st), -1);
+  PA_HIP_OR(hipStreamSynchronize(st), -1);
+  return hbad ? 1 : 0;
 }
 
 }  // namespace pa

@@ -401,6 +401,7 @@ struct Knobs {
   int f32_rows;          // Float32 SELL rows per lane (matrices built afterwards): 4 (16 B packs), 2 (8 B), 0 auto
   int tri_pack;          // triple SELL: bit 2 pair slices, bit 0 their Float32 per-triple value packs
   int spmv_uniform;      // Float64 short pattern rows: the uniform layout (build_uniform)
+  int scatter_wide;      // ordered vector scatter: 64-bit sort keys and payloads even when 32 bits fit
 };
 // the knobs of the call running on this thread (outside a call: a snapshot
 // of the process defaults)
@@ -521,6 +522,15 @@ struct CooList {
   DevBuf<void> V;
   int64_t n = 0;
 };
+// The ordered scatter of n pairs (id, V) into one part's values and its
+// gather twin (pa_coo.hip; pa_vec_scatter / pa_vec_gather).  I, V, out are
+// device arrays; global: I holds Int64 gids looked up in (sgid, slid).  Both
+// return 1 when an id has no lid (the scatter then wrote nothing), -1 on a
+// HIP error, and have completed on st when they return.
+int vec_scatter(int dtype, int64_t nl, void* v, bool global, int index_bytes, bool set, bool zero_first, bool wide,
+                int64_t n, void* I, const void* V, const uint64_t* sgid, const int64_t* slid, hipStream_t st);
+int vec_gather(int dtype, int64_t nl, const void* v, bool global, int index_bytes, bool absent_zero, int64_t n,
+               const void* I, void* out, const uint64_t* sgid, const int64_t* slid, hipStream_t st);
 }  // namespace pa
 
 struct pa_xchg {

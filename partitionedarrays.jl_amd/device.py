@@ -377,12 +377,88 @@ class DeviceVector:
         b, bp = _lib.scalar_buf(v, self.dtype)
         _lib.call("pa_vec_fill", self.h, bp)
 
+    def as_array(self, dtype=None) -> "DeviceArray":
+        """the values as a DeviceArray (pa_vec_device_ptr), reinterpreted as
+        `dtype` when given (e.g. Int64 ids kept in a Float64 vector)"""
+        dtype = np.dtype(dtype or self.dtype)
+        nbytes = self.n * self.dtype.itemsize
+        if nbytes % dtype.itemsize:
+            raise ValueError(f"as_array: {nbytes} bytes are no whole number of {dtype} values")
+        return DeviceArray(self.device_ptr(), nbytes // dtype.itemsize, dtype, self)
+
+    def scatter(self, idx: DeviceIndex, ids, vals, ids_global=False, op=_lib.PA_SCATTER_ADD, zero_first=False):
+        """pa_vec_scatter: values[lid(ids[k])] += vals[k] (or = with
+        PA_SCATTER_SET) in input order; with zero_first from zero(T) everywhere
+        (the COO constructor).  ids: 1-based lids (Int32 / Int64), or Int64
+        gids when ids_global — an Int64 array is then translated to lids in
+        place.  ids, vals: host arrays, or both DeviceArray."""
+        n, ib, on_device, ip, keep = _ids_arg(ids, ids_global, writable=ids_global)
+        if on_device != isinstance(vals, DeviceArray):
+            raise TypeError("scatter: ids and vals must both be host arrays or both DeviceArray")
+        if on_device:
+            if vals.dtype != self.dtype or vals.n != n:
+                raise ValueError("scatter: vals must hold one value of the vector's type per id")
+            vp = C.c_void_p(vals.ptr)
+        else:
+            vals = np.ascontiguousarray(vals, dtype=self.dtype).ravel()
+            if len(vals) != n:
+                raise ValueError("scatter: ids and vals must have the same length")
+            vp = vals.ctypes.data_as(C.c_void_p)
+        _lib.call("pa_vec_scatter", self.h, idx.h, _lib.PA_IDS_GLOBAL if ids_global else _lib.PA_IDS_LOCAL, ib,
+                  int(op), 1 if zero_first else 0, 1 if on_device else 0, n, ip, vp)
+        if keep is not None:  # ids was no contiguous Int64 array: hand the lids back
+            ids[...] = keep[0].reshape(np.shape(ids))
+
+    def gather(self, idx: DeviceIndex, ids, ids_global=False, absent_zero=False, out=None):
+        """pa_vec_gather: values[lid(ids[k])] as a host array (ids a host
+        array), or into the DeviceArray `out` (ids a DeviceArray).  An absent
+        gid reads zero with absent_zero, else it is an error."""
+        n, ib, on_device, ip, _ = _ids_arg(ids, ids_global, writable=False)
+        if on_device:
+            if not isinstance(out, DeviceArray) or out.dtype != self.dtype or out.n != n:
+                raise TypeError("gather: device ids need a DeviceArray `out` of the vector's type, one value per id")
+            op = C.c_void_p(out.ptr)
+        else:
+            out = np.empty(n, dtype=self.dtype)
+            op = out.ctypes.data_as(C.c_void_p)
+        _lib.call("pa_vec_gather", self.h, idx.h, _lib.PA_IDS_GLOBAL if ids_global else _lib.PA_IDS_LOCAL, ib,
+                  1 if absent_zero else 0, 1 if on_device else 0, n, ip, op)
+        return out
+
     def __del__(self):
         try:
             if getattr(self, "h", None) and _lib._lib is not None and not sys.is_finalizing():
                 _lib._lib.pa_vec_destroy(self.h)
         except Exception:
             pass
+
+
+class DeviceArray:
+    """A device array the caller owns, passed to the library by address
+    (on_device = 1 of pa_vec_scatter / pa_vec_gather): `n` values of `dtype`
+    at `ptr` on the part's device; `owner` keeps the allocation alive."""
+
+    def __init__(self, ptr: int, n: int, dtype, owner=None):
+        self.ptr, self.n, self.dtype, self.owner = int(ptr), int(n), np.dtype(dtype), owner
+
+
+def _ids_arg(ids, ids_global, writable):
+    """(n, index_bytes, on_device, pointer, keep) of an id array: lids cross
+    as Int32 or Int64 as given, gids as Int64.  keep = [the Int64 copy] when
+    `writable` ids (an ndarray) had to be copied, so that the caller can hand
+    the translated ids back."""
+    if isinstance(ids, DeviceArray):
+        if ids.dtype not in (np.dtype(np.int32), np.dtype(np.int64)) or (ids_global and ids.dtype != np.dtype(np.int64)):
+            raise TypeError("ids on the device must be Int64 (gids, lids) or Int32 (lids)")
+        return ids.n, ids.dtype.itemsize, True, C.c_void_p(ids.ptr), None
+    a = np.asarray(ids)
+    if a.size and a.dtype.kind not in "iu":
+        raise TypeError("ids must be integers")
+    want = np.int32 if (a.dtype == np.int32 and not ids_global) else np.int64
+    same = isinstance(ids, np.ndarray) and ids.dtype == want and ids.flags.c_contiguous and (ids.flags.writeable or not writable)
+    b = ids.reshape(-1) if same else np.ascontiguousarray(a, dtype=want).ravel().copy()
+    keep = [b] if (writable and not same and isinstance(ids, np.ndarray) and ids.flags.writeable) else None
+    return b.size, b.dtype.itemsize, False, b.ctypes.data_as(C.c_void_p), keep
 
 
 class DeviceCOO:

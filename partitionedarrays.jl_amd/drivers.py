@@ -2,6 +2,9 @@
 
 * `fdm_problem`  — test_fdm.jl:8-110 (3D 7-point FD Poisson, COO assembly,
   add_gids, PSparseMatrix(I,J,V,rows,cols; ids=:local)), vectorised.
+* `fem_sa_problem` — test_fem_sa.jl (2D Q1 FE, COO assembly on the device);
+  `fem_sa_problem_coo_rhs` builds its load vector on the device too, from the
+  COO pairs of `fem_sa_rhs_coo` (PVector(I, V, rows; ids=:global)).
 * `stencil_partition` / `stencil_operator` — Cartesian part boxes of the 7-pt
   FD operator and of the 27-pt Q1-hex FE operator (test_fem_sa.jl's pattern
   in 3D), assembled row-wise as test_fdm.jl does (each part
@@ -190,6 +193,48 @@ def fem_sa_problem(parts: PData, nx=10, init=None):
     x0h, xh = init(cols)
     A = PSparseMatrix.from_coo(coo, None, None, rows, cols, ids="global", init=mat_init)
     b = PVector.from_host(bh, rows)
+    assemble_(b)
+    return A, b, PVector.from_host(x0h, cols), PVector.from_host(xh, cols)
+
+
+def fem_sa_rhs_coo(parts: PData, nx=10):
+    """The load vector of test_fem_sa.jl as COO pairs (I, V), I in global
+    ids: one pair (grow, u(x) = 1.0) per boundary node of every owned cell, in
+    the touch order of test_fem_sa.jl:86-101 (owned cells in oid order, a
+    cell's nodes in CartesianIndices((2,2)) order).  Ghost rows included."""
+    nsn = nx + 1
+    cart = len(parts.shape) == 2
+    cells = prange_cartesian(parts, (nx, nx)) if cart else prange_linear(parts, nx * nx)
+
+    def pairs(s):
+        g = s.lid_to_gid[s.oid_to_lid - 1] - 1
+        cx, cy = g % nx, g // nx
+        # a cell's nodes (cx + ex, cy + ey), ex fastest
+        nxs = np.stack([cx, cx + 1, cx, cx + 1], 1).ravel()
+        nys = np.stack([cy, cy, cy + 1, cy + 1], 1).ravel()
+        bnd = (nxs == 0) | (nxs == nx) | (nys == 0) | (nys == nx)
+        I = (1 + nxs + nsn * nys)[bnd].astype(np.int64)
+        return I, np.ones(len(I))
+    return unzip(map_parts(pairs, cells.partition), 2)
+
+
+def fem_sa_problem_coo_rhs(parts: PData, nx=10, init=None):
+    """fem_sa_problem with the load vector built on the device: b =
+    PVector(I, V, rows; ids=:global) over fem_sa_rhs_coo's pairs
+    (pa_vec_scatter; the same additions in the same order as the
+    global_view loop of test_fem_sa.jl:86-101), then assemble!(b).  No
+    host-filled vector is uploaded."""
+    from .prange import add_gids_
+    from .pvector import COO, assemble_
+    mat_init = init
+    rows, cols, I, J, V, _, init = fem_sa_cells(parts, nx)
+    coo = COO.from_host(I, J, V, rows)
+    assemble_(coo, rows)
+    add_gids_(cols, coo.global_cols())
+    x0h, xh = init(cols)
+    A = PSparseMatrix.from_coo(coo, None, None, rows, cols, ids="global", init=mat_init)
+    Ib, Vb = fem_sa_rhs_coo(parts, nx)
+    b = PVector.from_coo(Ib, Vb, rows, ids="global")
     assemble_(b)
     return A, b, PVector.from_host(x0h, cols), PVector.from_host(xh, cols)
 

@@ -16,11 +16,12 @@ import weakref
 import numpy as np
 
 from . import _lib
-from .backends import PData, exchange, map_parts, unzip
-from .device import (DeviceCOO, DeviceMatrix, DeviceMatrixExchanger, DeviceVector, Task, contexts,
+from .backends import PData, exchange, get_part_ids, map_parts, unzip
+from .device import (DeviceArray, DeviceCOO, DeviceMatrix, DeviceMatrixExchanger, DeviceVector, Task, contexts,
                      device_exchanger, device_index, device_index_gids)
 from .helpers import Table, counts_to_ptrs, trace_setup
-from .prange import Exchanger, PRange, _cached_eq, empty_exchanger, hids_are_equal, oids_are_equal
+from .prange import (Exchanger, PRange, _cached_eq, add_gids_, empty_exchanger, hids_are_equal, oids_are_equal,
+                     prange_linear)
 
 
 # ---------------------------------------------------------------------------
@@ -196,6 +197,33 @@ class PVector(_ExprOps):
             dv.upload(h)
         return a
 
+    @staticmethod
+    def from_coo(I: PData, V: PData, rows_or_n, ids, dtype=None) -> "PVector":
+        """PVector(I, V, rows; ids=:global|:local) (Interfaces.jl:1887-1918):
+        values[lid] += V[i] from zero, in input order, on the device
+        (pa_vec_scatter); with ids="global" the Int64 arrays of I are
+        translated to lids in place, as to_lids! does there.  With a number n
+        instead of rows it is PVector(I, V, n; ids=:global) (1920-1932):
+        rows = PRange(parts, n) and add_gids!(rows, I) first.  I, V: PData of
+        host arrays, or of DeviceArray (rows form only)."""
+        if ids not in ("global", "local"):
+            raise ValueError("PVector(I, V, rows; ids): ids must be 'global' or 'local'")
+        if isinstance(rows_or_n, PRange):
+            rows = rows_or_n
+        else:
+            if ids != "global":
+                raise ValueError("PVector(I, V, n; ids): ids must be 'global'")
+            rows = prange_linear(get_part_ids(I), int(rows_or_n))
+            add_gids_(rows, I)
+        if dtype is None:
+            v0 = V.parts[0]
+            dtype = v0.dtype if isinstance(v0, DeviceArray) else np.asarray(v0).dtype
+        if np.dtype(dtype) not in _lib.DTYPES:
+            raise TypeError(f"PVector(I, V, rows): element type {np.dtype(dtype)} is not held on the device; pass dtype")
+        a = PVector.undef(rows, dtype)
+        _scatter_parts(a, I, V, ids, _lib.PA_SCATTER_ADD, zero_first=True)
+        return a
+
     def to_host(self) -> PData:
         return map_parts(lambda v: v.download(), self.values)
 
@@ -237,6 +265,96 @@ def copyto_(a: PVector, b: PVector) -> PVector:
     for da, db, xa, xb in zip(a.values.parts, b.values.parts, ia, ib):
         _lib.call("pa_vec_copy", da.h, xa, db.h, xb, 1 if same else 0)
     return a
+
+
+def _part_index(v: PVector, glob: bool):
+    """the device index sets of v's parts (with their gid tables when glob)"""
+    mk = device_index_gids if glob else device_index
+    return [mk(c, s) for c, s in zip(contexts(v.rows.partition), v.rows.partition.parts)]
+
+
+def _scatter_parts(v: PVector, I: PData, V: PData, ids, op, zero_first=False):
+    if I.part_ids != v.values.part_ids or V.part_ids != v.values.part_ids:
+        raise ValueError("PVector(I, V, rows): partitioned data over different parts")
+    glob = ids == "global"
+    for dv, x, i, w in zip(v.values.parts, _part_index(v, glob), I.parts, V.parts):
+        dv.scatter(x, i, w, ids_global=glob, op=op, zero_first=zero_first)
+    return v
+
+
+def add_coo_(v: PVector, I: PData, V: PData, ids="global") -> PVector:
+    """The batched `view[I] .+= V` over global_view(v, v.rows) (ids="global")
+    or local_view(v, v.rows) (ids="local"): v[I[k]] += V[k] in input order on
+    every part, on the device (test_fem_sa.jl:86-101 as one call per part).
+    Int64 arrays of global ids are translated to lids in place, as in
+    PVector.from_coo."""
+    if ids not in ("global", "local"):
+        raise ValueError("add_coo_: ids must be 'global' or 'local'")
+    return _scatter_parts(v, I, V, ids, _lib.PA_SCATTER_ADD)
+
+
+class VectorView:
+    """One part's GlobalView / LocalView of a PVector (Interfaces.jl:
+    2004-2069) with batched access: get(ids) = view[ids], set_(ids, vals) =
+    `view[ids] = vals` (a repeated id keeps its last value), add_(ids, vals)
+    = `view[ids] .+= vals` in input order.  The caller's ids stay as they are.
+
+    kind "local": ids are lids of the vector's own range (out of range: an
+    error).  kind "global": ids are gids; a read of a gid that is not a
+    local id is an error (gid_to_lid[g], 2062-2065).  kind "mapped"
+    (local_view over another range): ids are lids of that range, `gids` its
+    lid_to_gid; an id the vector does not store reads zero(T) (2019-2026) and
+    cannot be written (2027-2031)."""
+
+    def __init__(self, dv: DeviceVector, idx, kind, gids=None):
+        self.dv, self.idx, self.kind, self.gids = dv, idx, kind, gids
+
+    def _ids(self, ids):
+        ids = np.asarray(ids)
+        if self.kind != "mapped":
+            return ids.copy()
+        ids = ids.astype(np.int64).ravel()
+        if len(ids) and (ids.min() < 1 or ids.max() > len(self.gids)):
+            raise _lib.PAError("local_view: a local id is out of range (BoundsError)")
+        return self.gids[ids - 1]
+
+    def get(self, ids):
+        return self.dv.gather(self.idx, self._ids(ids), ids_global=self.kind != "local",
+                              absent_zero=self.kind == "mapped")
+
+    def set_(self, ids, vals):
+        self.dv.scatter(self.idx, self._ids(ids), vals, ids_global=self.kind != "local", op=_lib.PA_SCATTER_SET)
+        return self
+
+    def add_(self, ids, vals):
+        self.dv.scatter(self.idx, self._ids(ids), vals, ids_global=self.kind != "local", op=_lib.PA_SCATTER_ADD)
+        return self
+
+
+def global_view(v: PVector, rows: PRange = None) -> PData:
+    """global_view(a, rows) (Interfaces.jl:2037-2043): per part, the values
+    indexed by global ids; only over the vector's own rows (2038)."""
+    if rows is not None and rows is not v.rows:
+        raise NotImplementedError("global_view(a, rows): only for rows === a.rows (Interfaces.jl:2038)")
+    views = [VectorView(dv, x, "global") for dv, x in zip(v.values.parts, _part_index(v, True))]
+    return PData(v.values.backend, v.values.part_ids, views, v.values.shape)
+
+
+def local_view(v: PVector, rows: PRange = None) -> PData:
+    """local_view(a, rows) (Interfaces.jl:1994-2002): per part, the values
+    indexed by the local ids of rows.  Over the vector's own rows these are
+    its lids; over another range each lid is mapped to its gid on the host
+    (find_lid_map's role) and looked up in the vector's gid table on the
+    device."""
+    p = v.values
+    if rows is None or rows is v.rows:
+        views = [VectorView(dv, x, "local") for dv, x in zip(p.parts, _part_index(v, False))]
+    else:
+        if rows.partition.part_ids != p.part_ids:
+            raise ValueError("local_view: rows over different parts")
+        views = [VectorView(dv, x, "mapped", np.asarray(s.lid_to_gid, dtype=np.int64))
+                 for dv, x, s in zip(p.parts, _part_index(v, True), rows.partition.parts)]
+    return PData(p.backend, p.part_ids, views, p.shape)
 
 
 def _scalar_kind(a, dtype):
