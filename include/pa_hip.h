@@ -529,6 +529,59 @@ int pa_mat_fillstored(pa_mat* A, const void* v);
 /* nonzeros(A) in CSC nz order, ghost rows included (the device keeps the
  * ghost rows' values beside the SELL slots for exchange!/assemble!(A)).  */
 int pa_mat_get_values(const pa_mat* A, void* nzval);
+/* ---- entry views of a PSparseMatrix --------------------------------------
+ * The reads and writes of local_view / global_view over a matrix
+ * (Interfaces.jl:2277-2298 over the LocalView / GlobalView getindex and
+ * setindex! of 2004-2069), batched and on the device: the fixed-pattern
+ * re-assembly loop `fillstored!(A, 0); a[gi, gj] += ke[i, j]; assemble!(A)`
+ * without a host copy of nzval.
+ * pa_mat_scatter: the n entries (I[k], J[k], V[k]) written into the stored
+ * values of one part in input order, a[i, j] += v (op PA_SCATTER_ADD) or
+ * a[i, j] = v (PA_SCATTER_SET: the last entry of an (i, j) in input order
+ * stays).  The result equals the sequential loop bit for bit whatever the
+ * duplicates: each entry's value index is looked up in the matrix's entry
+ * table, the entries are sorted stably by it and each value's entries are
+ * added onto it in input order by one thread, with plain adds (complex
+ * values componentwise), no atomics — pa_vec_scatter's pass over the value
+ * array.  Afterwards the copies of the values that the SpMV layouts keep
+ * (side rows, triple SELL, uniform layout) are refreshed on the same stream,
+ * so the next mul! / cg! / exchange!(A) / assemble!(A) / pa_mat_get_values
+ * sees the new values.
+ * pa_mat_gather: out[k] = a[I[k], J[k]].
+ * Ids: PA_IDS_LOCAL: 1-based lids of rows / cols (index_bytes 4 or 8); one
+ * outside 1..num_lids is an error (BoundsError).  PA_IDS_GLOBAL: 1-based
+ * Int64 gids (index_bytes 8), looked up in the gid tables of rows and cols
+ * (pa_index_set_gids); a gid that is no local id of its range is an error
+ * (KeyError), except in pa_mat_gather with absent_zero = 1, where it reads
+ * zero(T) (the LocalView read over another range, 2019-2026).  I and J are
+ * never modified (the matrix views do not call to_lids!).  rows and cols
+ * must be the index sets the matrix was built with.
+ * Unstored entries: a valid (i, j) that the pattern does not store reads
+ * zero(T), as SparseArrays' getindex does.  A write to it is an error: the
+ * reference would insert the entry into the local CSC and change the
+ * pattern; the device pattern is fixed (a deviation).
+ * Every id of a call is checked before the first write: a failed call leaves
+ * A unchanged.  n = 0 is legal.  on_device = 1: I, J and V (pa_mat_gather:
+ * out) are device arrays on the part's device, otherwise host arrays
+ * consumed before the call returns.  The work runs on the part's compute
+ * stream, ordered with the part's other work.
+ * The entry table — the sorted keys row_lid * num_lids(cols) + col_lid of
+ * the stored entries (ghost rows and long rows included) with their value
+ * indices, 16 B per stored entry — is built by a matrix's first view call
+ * and kept; a matrix that never opens a view holds only the (row, col) lids
+ * of its ghost-row nonzeros (8 B each).  Matrices from pa_mat_from_csc /
+ * _csr / _coo[_csr] / _dcoo[_csr]; a pa_mat_stencil matrix has no nonzero
+ * map and fails with a message, as pa_mat_set_values does.                 */
+int pa_mat_scatter(pa_mat* A, pa_index* rows, pa_index* cols, int ids_kind,
+                   int index_bytes, int op, int on_device, int64_t n,
+                   const void* I, const void* J, const void* V);
+int pa_mat_gather(const pa_mat* A, pa_index* rows, pa_index* cols, int ids_kind,
+                  int index_bytes, int absent_zero, int on_device, int64_t n,
+                  const void* I, const void* J, void* out);
+/* The entry table of A: *entries = the stored entries it holds (the part's
+ * owned-row nonzeros + its ghost-row nonzeros), 0 while no view call has
+ * built it; *bytes = the device memory it takes.                          */
+int pa_mat_entry_info(const pa_mat* A, int64_t* entries, int64_t* bytes);
 /* matrix_exchanger(values, rows, cols) (Interfaces.jl:2300-2372): the
  * Exchanger whose lids are CSC nz positions k (1-based, Int64 as Julia's
  * Table{Int}): k_rcv = nonzeros of ghost rows grouped by owner, k_snd = the

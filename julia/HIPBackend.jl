@@ -23,7 +23,9 @@
 #     exchange!(I, J, V, rows) (2494-2592), the COO constructor
 #     PVector(init, I, V, rows; ids) (1887-1932) and batched reads and writes
 #     through global / local ids (view_add!, view_set!, view_get: the
-#     global_view / local_view access of 1994-2069 without a download);
+#     global_view / local_view access of 1994-2069 without a download; the
+#     same three over the stored entries (i, j) of a PSparseMatrix,
+#     2277-2298: the re-assembly loop of a fixed pattern);
 #   * everything else (PRange, Exchanger, add_gids!, gather/scatter setup
 #     collectives) runs unchanged on the host parts.
 #
@@ -763,6 +765,73 @@ function view_get(a::HIPVector{T}, I::HIPData; ids::Symbol, absent_zero::Bool=fa
   hs, ih = dev_vec(a), _view_idx(a, ids)
   out = [_vec_gather(hs[i], ih[i], ids, absent_zero, _ids_vector(I.parts[i], ids), T)
          for i in eachindex(a.values.parts)]
+  HIPData(out, a.values.ctxs, a.values.backend)
+end
+
+# ---- entry views of a PSparseMatrix (Interfaces.jl:2277-2298) ---------------
+# The batched forms of `view[i, j] += v`, `view[i, j] = v` and `view[i, j]`
+# over global_view(a, a.rows, a.cols) (ids = :global) / local_view(a, a.rows,
+# a.cols) (ids = :local), one pa_mat_scatter / pa_mat_gather per part over the
+# stored entries: the re-assembly loop of a fixed pattern without a download
+# of nzval.  I and J are left as they are; an (i, j) the pattern does not
+# store reads zero(T) and cannot be written (the device pattern is fixed).
+function _mat_scatter!(h::Ptr{Cvoid}, rh::Ptr{Cvoid}, ch::Ptr{Cvoid}, ids::Symbol, op::Cint,
+                       I::Vector{Ti}, J::Vector{Ti}, V::Vector{T}) where {Ti<:Union{Int32,Int64},T<:DeviceEltype}
+  @assert length(I) == length(J) == length(V)
+  check(ccall((:pa_mat_scatter, libpa), Cint,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Cint, Cint, Int64, Ptr{Ti}, Ptr{Ti}, Ptr{T}),
+              h, rh, ch, _ids_kind(ids), Cint(sizeof(Ti)), op, Cint(0), length(I), I, J, V))
+end
+function _mat_gather(h::Ptr{Cvoid}, rh::Ptr{Cvoid}, ch::Ptr{Cvoid}, ids::Symbol, absent_zero::Bool,
+                     I::Vector{Ti}, J::Vector{Ti}, ::Type{T}) where {Ti<:Union{Int32,Int64},T<:DeviceEltype}
+  @assert length(I) == length(J)
+  out = Vector{T}(undef, length(I))
+  check(ccall((:pa_mat_gather, libpa), Cint,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Cint, Cint, Int64, Ptr{Ti}, Ptr{Ti}, Ptr{T}),
+              h, rh, ch, _ids_kind(ids), Cint(sizeof(Ti)), Cint(absent_zero), Cint(0), length(I), I, J, out))
+  out
+end
+# row and column ids in one width (Int32 only when both are Int32 lids)
+function _ids_pair(I, J, ids::Symbol)
+  Ii, Ji = _ids_vector(I, ids), _ids_vector(J, ids)
+  eltype(Ii) === eltype(Ji) ? (Ii, Ji) : (Int64.(Ii), Int64.(Ji))
+end
+_mat_view_idx(r::PRange, ids::Symbol) =
+  [(ids === :global ? _idx_gids_handle : _idx_handle)(r.partition.ctxs[i], r.partition.parts[i])
+   for i in eachindex(r.partition.parts)]
+
+function _mat_scatter_parts!(a::HIPMatrix{T}, I::HIPData, J::HIPData, V::HIPData, ids::Symbol,
+                             op::Cint) where {T<:DeviceEltype}
+  @assert ids in (:global, :local)
+  hs = dev_mat(a)
+  rh, ch = _mat_view_idx(a.rows, ids), _mat_view_idx(a.cols, ids)
+  for i in eachindex(a.values.parts)
+    Ii, Ji = _ids_pair(I.parts[i], J.parts[i], ids)
+    _mat_scatter!(hs[i], rh[i], ch[i], ids, op, Ii, Ji, convert(Vector{T}, V.parts[i]))
+  end
+  mark_device_newer!(a)
+end
+
+"""`view[I[k], J[k]] += V[k]` for every k in input order, over
+`global_view(a, a.rows, a.cols)` (ids = :global) or `local_view(a, a.rows,
+a.cols)` (ids = :local), per part, on the device."""
+view_add!(a::HIPMatrix, I::HIPData, J::HIPData, V::HIPData; ids::Symbol) =
+  _mat_scatter_parts!(a, I, J, V, ids, PA_SCATTER_ADD)
+"""`view[I[k], J[k]] = V[k]` in input order (a repeated (i, j) keeps its last value)."""
+view_set!(a::HIPMatrix, I::HIPData, J::HIPData, V::HIPData; ids::Symbol) =
+  _mat_scatter_parts!(a, I, J, V, ids, PA_SCATTER_SET)
+"""`view[I[k], J[k]]` per part; an entry the pattern does not store reads
+zero(T).  A gid that is not a local id reads zero(T) with absent_zero
+(LocalView, Interfaces.jl:2019-2026) and is an error without (GlobalView,
+2062-2065)."""
+function view_get(a::HIPMatrix{T}, I::HIPData, J::HIPData; ids::Symbol, absent_zero::Bool=false) where {T<:DeviceEltype}
+  @assert ids in (:global, :local)
+  hs = dev_mat(a)
+  rh, ch = _mat_view_idx(a.rows, ids), _mat_view_idx(a.cols, ids)
+  out = map(eachindex(a.values.parts)) do i
+    Ii, Ji = _ids_pair(I.parts[i], J.parts[i], ids)
+    _mat_gather(hs[i], rh[i], ch[i], ids, absent_zero, Ii, Ji, T)
+  end
   HIPData(out, a.values.ctxs, a.values.backend)
 end
 

@@ -24,7 +24,7 @@ from .pvector import (COO, CSC, CSR, PSparseMatrix, PVector, assemble_, axmy_, a
 from .pvector import (Broadcasted, ExprProgram, abs2, all_, any_, assign_, conj, encode_expr, eq, euclidean,  # noqa: F401
                       isequal, materialize, maximum, minimum, ne, sqeuclidean)
 from .pvector import async_assemble_, async_exchange_, record, wait_all  # noqa: F401
-from .pvector import VectorView, add_coo_, global_view, local_view  # noqa: F401
+from .pvector import MatrixView, VectorView, add_coo_, global_view, local_view  # noqa: F401
 from .device import DeviceArray  # noqa: F401
 from .ptimers import PTimer  # noqa: F401
 from . import drivers  # noqa: F401

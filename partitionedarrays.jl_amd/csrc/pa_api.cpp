@@ -103,9 +103,10 @@ int coo_row_order(int64_t nu, const int32_t* crow, const int32_t* ccol, const in
 void coo_slices(int64_t ns, int64_t nrows, int H, const int64_t* rowptr, const uint64_t* key2, int64_t ncols,
                 int64_t noids_c, const int32_t* lidx, int32_t* slen, int32_t* sghost, hipStream_t st);
 void coo_fill(int dtype, int64_t nnz, int64_t nu, const uint64_t* key2, const int64_t* idx2, const int64_t* rowptr,
-              const int64_t* soff, int H, int R, int64_t ncols, const int32_t* ccol, const void* cval,
-              const int64_t* gflag, const int64_t* grank, int64_t slots, int32_t* col, void* val, int64_t* nz_slot,
-              const int32_t* lidx, const int64_t* lptr, int32_t* lcol, int64_t long_off, hipStream_t st);
+              const int64_t* soff, int H, int R, int64_t ncols, const int32_t* crow, const int32_t* ccol,
+              const void* cval, const int64_t* gflag, const int64_t* grank, int64_t slots, int32_t* col, void* val,
+              int64_t* nz_slot, const int32_t* lidx, const int64_t* lptr, int32_t* lcol, int64_t long_off,
+              int32_t* grc, hipStream_t st);
 void launch_fill_i32(int64_t n, int32_t* a, int32_t v, hipStream_t st);
 void launch_spmv_long(const pa_mat* A, const void* x, void* y, const int32_t* ymap, bool has_alpha, int bmode,
                       const void* alpha, const void* beta, void* dotp, int64_t dot_base, hipStream_t st);
@@ -2317,8 +2318,9 @@ int pa_vec_gather(const pa_vec* v, pa_index* idx, int ids_kind, int index_bytes,
     HIPC(bO.alloc(obytes));
     dO = bO.p;
   }
-  const int rc = vec_gather(v->dtype, v->n, v->d, global, index_bytes, absent_zero != 0, n, dI, dO, idx->d_sgid,
-                            idx->d_slid, c->s_main);
+  // (a local id out of range is an error whatever absent_zero says)
+  const int rc = vec_gather(v->dtype, v->n, v->d, global, index_bytes, global && absent_zero != 0, n, dI, dO,
+                            idx->d_sgid, idx->d_slid, c->s_main);
   CHECK_ARG(rc >= 0, "pa_vec_gather: device pass failed");
   if (rc && global) PA_FAIL("pa_vec_gather: a global id is not a local id of the part (KeyError)");
   if (rc) PA_FAIL("pa_vec_gather: a local id is out of range (BoundsError)");
@@ -2374,12 +2376,16 @@ int mat_finish(std::unique_ptr<pa_mat>& A, const std::vector<int32_t>& slen, int
   return 0;
 }
 
-template <class Visit>
+// `each_nz(f)` calls f(row lid, col lid, nz position) (0-based) for every
+// input nonzero: the stored ghost rows' (row, col) are kept for the entry
+// views (pa_mat::d_ghost_rc).
+template <class Visit, class EachNz>
 int mat_from_visit(pa_ctx* c, int dtype, int64_t nrows_lids, int64_t ncols_lids, int64_t in_nnz,
-                   const void* nzval, const pa_index* rows, const pa_index* cols, Visit&& visit,
+                   const void* nzval, const pa_index* rows, const pa_index* cols, Visit&& visit, EachNz&& each_nz,
                    const char* range_error, bool csr, pa_mat** out) {
   const size_t S = dtype_size(dtype);
   std::unique_ptr<pa_mat> A = mat_start(c, dtype, rows->noids, ncols_lids);
+  A->nrows_lids = nrows_lids;
   A->csr = csr;
   A->csc_nnz = in_nnz;
   const int64_t nr = A->main.nrows;
@@ -2449,9 +2455,21 @@ int mat_from_visit(pa_ctx* c, int dtype, int64_t nrows_lids, int64_t ncols_lids,
     HIPC(hipMemcpy(A->main.val, hval.data(), nv * S, hipMemcpyHostToDevice));
   }
   if (upload_long(A.get(), L.lrows, lptr, lcol)) return -1;
+  if (A->n_gnz > 0) {
+    std::vector<int32_t> grc(2 * A->n_gnz, -1);
+    each_nz([&](int64_t I, int64_t J, int64_t p) {
+      if (A->h_nz_slot[p] >= 0 || lpos[p] >= 0) return;
+      const int64_t g = -A->h_nz_slot[p] - 1;
+      if (I < 0 || I >= nrows_lids || J < 0 || J >= ncols_lids) return;  // (a ghost row of a CSR parent: unchecked so far)
+      grc[2 * g] = (int32_t)I;
+      grc[2 * g + 1] = (int32_t)J;
+    });
+    HIPC(A->d_ghost_rc.upload(grc));
+  }
   // pattern slices need "x lid >= noids ⇔ ghost column" (contiguous layout)
   return mat_finish(A, slen, cols->noids, cols->own_contig && cols->ghost_contig, [&] {
-    return mat_from_visit(c, dtype, nrows_lids, ncols_lids, in_nnz, nzval, rows, cols, visit, range_error, csr, out);
+    return mat_from_visit(c, dtype, nrows_lids, ncols_lids, in_nnz, nzval, rows, cols, visit, each_nz, range_error, csr,
+                          out);
   }, out);
 }
 
@@ -2499,7 +2517,11 @@ int pa_mat_from_csc(pa_ctx* c, int dtype, int index_bytes, int64_t nrows_lids, i
     }
     return 0;
   };
-  return mat_from_visit(c, dtype, nrows_lids, ncols_lids, csc_nnz, nzval, rows, cols, visit,
+  auto each_nz = [&](auto&& f) {
+    for (int64_t J = 0; J < ncols_lids; ++J)
+      for (int64_t p = cp(J) - 1; p < cp(J + 1) - 1; ++p) f(rv(p) - 1, J, p);
+  };
+  return mat_from_visit(c, dtype, nrows_lids, ncols_lids, csc_nnz, nzval, rows, cols, visit, each_nz,
                         "CSC rowval out of range", false, out);
 }
 
@@ -2541,7 +2563,11 @@ int pa_mat_from_csr(pa_ctx* c, int dtype, int index_bytes, int Bi, int64_t nrows
       }
     return 0;
   };
-  return mat_from_visit(c, dtype, nrows_lids, ncols_lids, csr_nnz, nzval, rows, cols, visit,
+  auto each_nz = [&](auto&& f) {
+    for (int64_t I = 0; I < nrows_lids; ++I)
+      for (int64_t p = rp(I); p < rp(I + 1); ++p) f(I, cv(p), p);
+  };
+  return mat_from_visit(c, dtype, nrows_lids, ncols_lids, csr_nnz, nzval, rows, cols, visit, each_nz,
                         "CSR colval out of range", true, out);
 }
 
@@ -2685,6 +2711,7 @@ int mat_from_coo_impl(pa_ctx* c, int dtype, int index_bytes, int ids_global, int
   HIPC(cl2o.upload(cols->h_lid_to_ohid));
 
   std::unique_ptr<pa_mat> A = mat_start(c, dtype, rows->noids, ncols_lids);
+  A->nrows_lids = nrows_lids;
   A->csr = csr;
   A->csc_nnz = nu;
   const int64_t nrows = A->main.nrows;
@@ -2734,9 +2761,10 @@ int mat_from_coo_impl(pa_ctx* c, int dtype, int index_bytes, int ids_global, int
     HIPC(hipMemsetAsync(A->main.val, 0, nv * S, st));
   }
   if (nu > 0) HIPC(nzs.alloc(nu));
+  if (ngh > 0) HIPC(A->d_ghost_rc.alloc(2 * ngh));
   tr.mark("slices");
-  coo_fill(dtype, nnz, nu, key2, idx2, rowptr, A->main.off, A->H, A->R, ncols_lids, ccol, cval, gflag, grank,
-           A->main.slots, A->main.col, A->main.val, nzs, lidx_d, lptr_d, lcol_d, A->long_off, st);
+  coo_fill(dtype, nnz, nu, key2, idx2, rowptr, A->main.off, A->H, A->R, ncols_lids, crow, ccol, cval, gflag, grank,
+           A->main.slots, A->main.col, A->main.val, nzs, lidx_d, lptr_d, lcol_d, A->long_off, A->d_ghost_rc, st);
   HIPC(hipGetLastError());
   A->d_nz_slot = std::move(nzs);  // downloaded on first use (load_nz_map)
   A->nz_map = true;
@@ -3119,6 +3147,108 @@ int pa_mat_get_values(const pa_mat* A, void* nzval) {
   if (nv) HIPC(hipMemcpy(hval.data(), A->main.val, nv * S, hipMemcpyDeviceToHost));
   for (int64_t p = 0; p < A->csc_nnz; ++p)
     std::memcpy((unsigned char*)nzval + p * S, &hval[nz_index(A, p) * S], S);
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Entry views (pa_mat_scatter / pa_mat_gather): the (i, j) of a call become
+// value indices of main.val through the matrix's entry table (pa_coo.hip,
+// built by the first call), and the vector scatter / gather runs over
+// main.val with them as local ids.
+
+// the argument checks the two calls share, in vec_ids_check's words and order
+static int mat_ids_check(const char* who, const pa_mat* A, const pa_index* rows, const pa_index* cols, int ids_kind,
+                         int index_bytes, int64_t n, const void* I, const void* J, const void* vals) {
+  const std::string w = std::string(who) + ": ";
+  CHECK_ARG(ids_kind == PA_IDS_LOCAL || ids_kind == PA_IDS_GLOBAL, w + "ids_kind must be PA_IDS_LOCAL or PA_IDS_GLOBAL");
+  CHECK_ARG(index_bytes == 4 || index_bytes == 8, w + "index_bytes must be 4 or 8");
+  CHECK_ARG(ids_kind != PA_IDS_GLOBAL || index_bytes == 8, w + "ids=:global needs Int64 ids (index_bytes 8)");
+  CHECK_ARG(n >= 0, w + "negative length");
+  CHECK_ARG(A && rows && cols && (n == 0 || (I && J && vals)), w + "null argument");
+  CHECK_ARG(A->ctx == rows->ctx && A->ctx == cols->ctx, w + "the matrix and the index sets belong to different parts");
+  CHECK_ARG(A->nz_map, w + "matrix was not built from a CSC pattern");
+  CHECK_ARG(rows->nlids == A->nrows_lids && rows->noids == A->main.nrows && cols->nlids == A->ncols_lids,
+            w + "the index sets do not have the matrix's local ids");
+  CHECK_ARG(ids_kind != PA_IDS_GLOBAL || (rows->has_gids && cols->has_gids), w + "call pa_index_set_gids first");
+  return 0;
+}
+
+// the value indices (1-based, 0: none) of the n entries of a call, in vidx
+static int mat_value_ids(const char* who, const pa_mat* cA, const pa_index* rows, const pa_index* cols, bool global,
+                         int index_bytes, bool absent_zero, bool stored, int64_t n, const void* dI, const void* dJ,
+                         DevBuf<int64_t>& vidx) {
+  const std::string w = std::string(who) + ": ";
+  pa_mat* A = const_cast<pa_mat*>(cA);  // the table is built on first use, as the nz map is loaded
+  hipStream_t st = A->ctx->s_main;
+  CHECK_ARG(A->has_entries || mat_entry_table(A, rows, st) == 0, w + "building the entry table failed");
+  HIPC(vidx.alloc(n));
+  const int rc = mat_entry_ids(A, rows, cols, global, index_bytes, absent_zero, stored, n, dI, dJ, vidx, st);
+  CHECK_ARG(rc >= 0, w + "device pass failed");
+  if (rc == 1 && global) PA_FAIL(w + "a global id is not a local id of the part (KeyError)");
+  if (rc == 1) PA_FAIL(w + "a local id is out of range (BoundsError)");
+  if (rc == 2) PA_FAIL(w + "an entry (i, j) is not stored: the pattern on the device is fixed, no entry is inserted");
+  return 0;
+}
+
+int pa_mat_scatter(pa_mat* A, pa_index* rows, pa_index* cols, int ids_kind, int index_bytes, int op, int on_device,
+                   int64_t n, const void* I, const void* J, const void* V) {
+  CHECK_ARG(op == PA_SCATTER_ADD || op == PA_SCATTER_SET, "pa_mat_scatter: op must be PA_SCATTER_ADD or PA_SCATTER_SET");
+  if (mat_ids_check("pa_mat_scatter", A, rows, cols, ids_kind, index_bytes, n, I, J, V)) return -1;
+  if (n == 0) return 0;
+  pa_ctx* c = A->ctx;
+  TuneScope ts(c);
+  HIPC(hipSetDevice(c->device));
+  const bool global = ids_kind == PA_IDS_GLOBAL;
+  const size_t ibytes = (size_t)n * index_bytes;
+  DevBuf<void> bI, bJ, bV;
+  DevBuf<int64_t> vidx;
+  void *dI = nullptr, *dJ = nullptr, *dV = nullptr;
+  if (vec_stage(on_device, I, ibytes, bI, c->s_main, &dI) || vec_stage(on_device, J, ibytes, bJ, c->s_main, &dJ) ||
+      vec_stage(on_device, V, (size_t)n * dtype_size(A->dtype), bV, c->s_main, &dV))
+    return -1;
+  if (mat_value_ids("pa_mat_scatter", A, rows, cols, global, index_bytes, false, true, n, dI, dJ, vidx)) return -1;
+  const int64_t nv = nvals(A);
+  const bool wide = knobs().scatter_wide || (uint64_t)nv > (1ull << 32) || (uint64_t)n > (1ull << 32);
+  const int rc = vec_scatter(A->dtype, nv, A->main.val, false, 8, op == PA_SCATTER_SET, false, wide, n, vidx.p, dV,
+                             nullptr, nullptr, c->s_main);
+  CHECK_ARG(rc == 0, "pa_mat_scatter: device pass failed");
+  return refresh_side(A, c->s_main);
+}
+
+int pa_mat_gather(const pa_mat* A, pa_index* rows, pa_index* cols, int ids_kind, int index_bytes, int absent_zero,
+                  int on_device, int64_t n, const void* I, const void* J, void* out) {
+  if (mat_ids_check("pa_mat_gather", A, rows, cols, ids_kind, index_bytes, n, I, J, out)) return -1;
+  if (n == 0) return 0;
+  pa_ctx* c = A->ctx;
+  HIPC(hipSetDevice(c->device));
+  const bool global = ids_kind == PA_IDS_GLOBAL;
+  const size_t ibytes = (size_t)n * index_bytes, obytes = (size_t)n * dtype_size(A->dtype);
+  DevBuf<void> bI, bJ, bO;
+  DevBuf<int64_t> vidx;
+  void *dI = nullptr, *dJ = nullptr, *dO = out;
+  if (vec_stage(on_device, I, ibytes, bI, c->s_main, &dI) || vec_stage(on_device, J, ibytes, bJ, c->s_main, &dJ))
+    return -1;
+  if (!on_device) {
+    HIPC(bO.alloc(obytes));
+    dO = bO.p;
+  }
+  if (mat_value_ids("pa_mat_gather", A, rows, cols, global, index_bytes, global && absent_zero != 0, false, n, dI, dJ,
+                    vidx))
+    return -1;
+  // value index 0 (not stored, or an absent id that may read zero): zero(T)
+  const int rc = vec_gather(A->dtype, nvals(A), A->main.val, false, 8, true, n, vidx.p, dO, nullptr, nullptr, c->s_main);
+  CHECK_ARG(rc == 0, "pa_mat_gather: device pass failed");
+  if (!on_device) {
+    HIPC(hipMemcpyAsync(out, dO, obytes, hipMemcpyDeviceToHost, c->s_main));
+    HIPC(hipStreamSynchronize(c->s_main));
+  }
+  return 0;
+}
+
+int pa_mat_entry_info(const pa_mat* A, int64_t* entries, int64_t* bytes) {
+  CHECK_ARG(A, "null matrix");
+  if (entries) *entries = A->has_entries ? A->n_entries : 0;
+  if (bytes) *bytes = A->has_entries ? A->n_entries * 16 : 0;
   return 0;
 }
 

@@ -168,16 +168,20 @@ __global__ void k_fill_slots(int64_t nnz, const uint64_t* __restrict__ key2, con
   }
 }
 
-// ghost-row nonzeros in CSC order after the slots: nz_slot = -(rank+1)
+// ghost-row nonzeros in CSC order after the slots: nz_slot = -(rank+1);
+// grc keeps their (row lid, col lid) for the entry views (pa_mat::d_ghost_rc)
 template <typename T>
 __global__ void k_fill_ghost(int64_t nu, const int64_t* __restrict__ gflag, const int64_t* __restrict__ grank,
                              const T* __restrict__ cval, int64_t slots, T* __restrict__ val,
-                             int64_t* __restrict__ nz_slot) {
+                             int64_t* __restrict__ nz_slot, const int32_t* __restrict__ crow,
+                             const int32_t* __restrict__ ccol, int32_t* __restrict__ grc) {
   for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < nu; p += (int64_t)gridDim.x * blockDim.x)
     if (gflag[p]) {
       const int64_t g = grank[p];
       nz_slot[p] = -(g + 1);
       val[slots + g] = cval[p];
+      grc[2 * g] = crow[p];
+      grc[2 * g + 1] = ccol[p];
     }
 }
 
@@ -371,17 +375,18 @@ void coo_slices(int64_t ns, int64_t nrows, int H, const int64_t* rowptr, const u
 }
 
 void coo_fill(int dtype, int64_t nnz, int64_t nu, const uint64_t* key2, const int64_t* idx2, const int64_t* rowptr,
-              const int64_t* soff, int H, int R, int64_t ncols, const int32_t* ccol, const void* cval,
-              const int64_t* gflag, const int64_t* grank, int64_t slots, int32_t* col, void* val, int64_t* nz_slot,
-              const int32_t* lidx, const int64_t* lptr, int32_t* lcol, int64_t long_off, hipStream_t st) {
+              const int64_t* soff, int H, int R, int64_t ncols, const int32_t* crow, const int32_t* ccol,
+              const void* cval, const int64_t* gflag, const int64_t* grank, int64_t slots, int32_t* col, void* val,
+              int64_t* nz_slot, const int32_t* lidx, const int64_t* lptr, int32_t* lcol, int64_t long_off,
+              int32_t* grc, hipStream_t st) {
   const int64_t ngh = long_off - slots;
 #define PA_FILL(T)                                                                                             \
   if (nnz > 0)                                                                                                 \
     hipLaunchKernelGGL(k_fill_slots<T>, grid1(nnz), dim3(256), 0, st, nnz, key2, idx2, rowptr, soff, H, R,     \
                        ncols, ccol, (const T*)cval, col, (T*)val, nz_slot, lidx, lptr, lcol, long_off, ngh);   \
-  if (nu > 0)                                                                                                  \
+  if (nu > 0 && ngh > 0)                                                                                       \
     hipLaunchKernelGGL(k_fill_ghost<T>, grid1(nu), dim3(256), 0, st, nu, gflag, grank, (const T*)cval, slots, \
-                       (T*)val, nz_slot);
+                       (T*)val, nz_slot, crow, ccol, grc);
   switch (dtype) {
     case PA_F32: { PA_FILL(float) } break;
     case PA_F64: { PA_FILL(double) } break;
@@ -824,14 +829,15 @@ __global__ void k_vec_scatter(int64_t n, const K* __restrict__ key, const P* __r
 }
 
 // out[k] = v[lid(id k)]; an id without a lid reads zero(T), and sets *bad
-// unless it is an absent global id that may read as zero (LocalView, 2019-2026)
+// unless absent_zero: an absent global id that may read as zero (LocalView,
+// 2019-2026), or the 0 that mat_entry_ids gives an entry without a value
 template <typename T, bool GLOBAL, typename IT>
 __global__ void k_vec_gather(int64_t n, const IT* __restrict__ I, const uint64_t* __restrict__ sgid,
                              const int64_t* __restrict__ slid, int64_t nl, const T* __restrict__ v,
                              T* __restrict__ out, int absent_zero, int* __restrict__ bad) {
   for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
     const int64_t l = vec_lid<GLOBAL>(I[k], sgid, slid, nl);
-    if (l < 0 && !(GLOBAL && absent_zero)) *bad = 1;
+    if (l < 0 && !absent_zero) *bad = 1;
     out[k] = l < 0 ? zero_of<T>() : v[l];
   }
 }
@@ -928,8 +934,9 @@ int vec_scatter(int dtype, int64_t nl, void* v, bool global, int index_bytes, bo
 }
 
 // One part's gather: out[k] = v[lid of I[k]] (I, out: device arrays, n
-// entries).  absent_zero: an absent global id reads zero(T); otherwise, and
-// for a local id out of range, the call returns 1 (out is then unspecified).
+// entries).  absent_zero: an id without a lid reads zero(T) (pa_vec_gather
+// asks for it with global ids only); otherwise the call returns 1 (out is
+// then unspecified).
 // -1 on a HIP error.  The work is complete on return.
 int vec_gather(int dtype, int64_t nl, const void* v, bool global, int index_bytes, bool absent_zero, int64_t n,
                const void* I, void* out, const uint64_t* sgid, const int64_t* slid, hipStream_t st) {
@@ -948,6 +955,178 @@ int vec_gather(int dtype, int64_t nl, const void* v, bool global, int index_byte
   PA_HIP_OR(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, st), -1);
   PA_HIP_OR(hipStreamSynchronize(st), -1);
   return hbad ? 1 : 0;
+}
+
+// ---------------------------------------------------------------------------
+// Entry views of a PSparseMatrix (Interfaces.jl:2277-2298; pa_mat_scatter /
+// pa_mat_gather): the lookup from (row lid, col lid) to the value index in
+// main.val.  The entry table is derived from the layout the matrix already
+// keeps — the slots' columns, the long rows' CSR and the ghost rows' (row,
+// col) pairs — so the parent's colptr / rowval are not needed: one pass over
+// the value indices emits key = row_lid * ncols_lids + col_lid for every
+// index that holds a stored entry, the emitted pairs are compacted and
+// sorted by key, and a lookup is a binary search.
+
+// what k_entry_emit reads of a matrix
+struct EntrySrc {
+  int64_t slots, n_gnz, n_lnz, nrows, nslices, ncols, n_long;
+  int H, R;
+  const int64_t* off;         // main.off
+  const int32_t* col;         // main.col
+  const int32_t* kind;        // pa_mat::d_kind (null: every slice blocked)
+  const int32_t* oid_to_lid;  // of the rows (null: the identity)
+  const int32_t* grc;         // pa_mat::d_ghost_rc
+  const int32_t* long_row;
+  const int64_t* long_ptr;
+  const int32_t* long_col;
+};
+
+// value index t of main.val: flag[t] = 1 and key[t] = its entry's key when
+// it holds a stored entry, flag[t] = 0 for padding.  A slot t of slice s is
+// entry k of the slice's row w: t = off[s] + (k*64 + lane)*R + rr with
+// w = lane*R + rr (mat_from_visit, k_fill_slots), or w = rr*64 + lane in a
+// Float32 delta16 slice of 4 rows per lane (k_delta16 moved its rows).
+__global__ void k_entry_emit(EntrySrc a, uint64_t* __restrict__ key, int64_t* __restrict__ flag) {
+  const int64_t nv = a.slots + a.n_gnz + a.n_lnz;
+  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < nv; t += (int64_t)gridDim.x * blockDim.x) {
+    int64_t r = -1, c = -1;  // row lid, col lid
+    if (t < a.slots) {
+      int64_t lo = 0, hi = a.nslices;  // the last slice whose offset is <= t
+      while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (a.off[mid] <= t) lo = mid; else hi = mid;
+      }
+      const int64_t u = t - a.off[lo];
+      const int pos = (int)(u % a.H), lane = pos / a.R, rr = pos % a.R;
+      const bool il = a.R == 4 && a.kind && a.kind[lo] == kBkDelta16;
+      const int64_t oid = lo * a.H + (il ? rr * 64 + lane : lane * a.R + rr);
+      c = a.col[t];
+      if (oid < a.nrows && c >= 0) r = a.oid_to_lid ? a.oid_to_lid[oid] : oid;
+    } else if (t < a.slots + a.n_gnz) {
+      const int64_t g = t - a.slots;
+      r = a.grc[2 * g];
+      c = a.grc[2 * g + 1];
+    } else {
+      const int64_t q = t - a.slots - a.n_gnz;
+      int64_t lo = 0, hi = a.n_long;  // the long row whose CSR range holds q
+      while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (a.long_ptr[mid] <= q) lo = mid; else hi = mid;
+      }
+      const int64_t oid = a.long_row[lo];
+      c = a.long_col[q];
+      r = a.oid_to_lid ? a.oid_to_lid[oid] : oid;
+    }
+    const bool ok = r >= 0 && c >= 0;
+    flag[t] = ok ? 1 : 0;
+    key[t] = ok ? (uint64_t)r * (uint64_t)a.ncols + (uint64_t)c : 0;
+  }
+}
+
+// rank = exclusive scan of flag: the flagged value indices, in order
+__global__ void k_entry_compact(int64_t nv, const uint64_t* __restrict__ key, const int64_t* __restrict__ flag,
+                                const int64_t* __restrict__ rank, uint64_t* __restrict__ ekey,
+                                int64_t* __restrict__ eidx) {
+  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < nv; t += (int64_t)gridDim.x * blockDim.x)
+    if (flag[t]) {
+      ekey[rank[t]] = key[t];
+      eidx[rank[t]] = t;
+    }
+}
+
+// vidx[k] = 1 + the value index of entry (I[k], J[k]), or 0.  bad[0]: an id
+// without a lid (absent_zero: an absent global id is none); bad[1]: a valid
+// (i, j) the table does not hold.
+template <bool GLOBAL, typename IT>
+__global__ void k_entry_ids(int64_t n, const IT* __restrict__ I, const IT* __restrict__ J,
+                            const uint64_t* __restrict__ rsgid, const int64_t* __restrict__ rslid, int64_t nrl,
+                            const uint64_t* __restrict__ csgid, const int64_t* __restrict__ cslid, int64_t ncl,
+                            const uint64_t* __restrict__ ekey, const int64_t* __restrict__ eidx, int64_t ne,
+                            int absent_zero, int64_t* __restrict__ vidx, int* __restrict__ bad) {
+  for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = vec_lid<GLOBAL>(I[k], rsgid, rslid, nrl);
+    const int64_t j = vec_lid<GLOBAL>(J[k], csgid, cslid, ncl);
+    int64_t v = 0;
+    if (i < 0 || j < 0) {
+      if (!(GLOBAL && absent_zero)) bad[0] = 1;
+    } else {
+      const uint64_t q = (uint64_t)i * (uint64_t)ncl + (uint64_t)j;
+      int64_t lo = 0, hi = ne;
+      while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (ekey[mid] < q) lo = mid + 1; else hi = mid;
+      }
+      if (lo < ne && ekey[lo] == q) v = eidx[lo] + 1;
+      else bad[1] = 1;
+    }
+    vidx[k] = v;
+  }
+}
+
+int mat_entry_table(pa_mat* A, const pa_index* rows, hipStream_t st) {
+  const int64_t nv = A->main.slots + A->n_gnz + A->n_lnz;
+  A->d_ekey.reset();
+  A->d_eidx.reset();
+  A->n_entries = 0;
+  if (nv > 0) {
+    DevBuf<uint64_t> key;
+    DevBuf<int64_t> flag, rank;
+    int64_t last[2] = {0, 0};
+    PA_HIP_OR(key.alloc(nv), -1);
+    PA_HIP_OR(flag.alloc(nv), -1);
+    PA_HIP_OR(rank.alloc(nv), -1);
+    const EntrySrc a = {A->main.slots, A->n_gnz, A->n_lnz, A->main.nrows, A->main.nslices, A->ncols_lids, A->n_long,
+                        A->H, A->R, A->main.off, A->main.col, A->d_kind, rows->own_contig ? nullptr : rows->d_oid_to_lid.p,
+                        A->d_ghost_rc, A->d_long_row, A->d_long_ptr, A->d_long_col};
+    hipLaunchKernelGGL(k_entry_emit, grid1(nv), dim3(256), 0, st, a, key.p, flag.p);
+    PA_HIP_OR(hipGetLastError(), -1);
+    PA_HIP_OR(exclusive_sum(flag, rank, nv, st), -1);
+    PA_HIP_OR(hipMemcpyAsync(&last[0], rank.p + nv - 1, 8, hipMemcpyDeviceToHost, st), -1);
+    PA_HIP_OR(hipMemcpyAsync(&last[1], flag.p + nv - 1, 8, hipMemcpyDeviceToHost, st), -1);
+    PA_HIP_OR(hipStreamSynchronize(st), -1);
+    const int64_t ne = last[0] + last[1];
+    if (ne > 0) {
+      PA_HIP_OR(A->d_ekey.alloc(ne), -1);
+      PA_HIP_OR(A->d_eidx.alloc(ne), -1);
+      hipLaunchKernelGGL(k_entry_compact, grid1(nv), dim3(256), 0, st, nv, key.p, flag.p, rank.p, A->d_ekey.p,
+                         A->d_eidx.p);
+      PA_HIP_OR(hipGetLastError(), -1);
+      PA_HIP_OR(hipStreamSynchronize(st), -1);
+      key.reset(), flag.reset(), rank.reset();  // before the sort takes its buffers
+      const uint64_t maxk = (uint64_t)(A->nrows_lids > 0 ? A->nrows_lids : 1) * (uint64_t)A->ncols_lids;
+      PA_HIP_OR(sort_pairs(A->d_ekey, A->d_eidx, ne, bits_for(maxk), st), -1);
+    }
+    A->n_entries = ne;
+  }
+  A->has_entries = true;
+  return 0;
+}
+
+int mat_entry_ids(const pa_mat* A, const pa_index* rows, const pa_index* cols, bool global, int index_bytes,
+                  bool absent_zero, bool stored, int64_t n, const void* I, const void* J, int64_t* vidx,
+                  hipStream_t st) {
+  if (n <= 0) return 0;
+  DevBuf<int> bad;
+  int hbad[2] = {0, 0};
+  PA_HIP_OR(bad.alloc(2), -1);
+  PA_HIP_OR(hipMemsetAsync(bad, 0, 2 * sizeof(int), st), -1);
+#define PA_ENTRY_IDS(G, IT)                                                                                          \
+  hipLaunchKernelGGL((k_entry_ids<G, IT>), grid1(n), dim3(256), 0, st, n, (const IT*)I, (const IT*)J,                \
+                     rows->d_sgid.p, rows->d_slid.p, rows->nlids, cols->d_sgid.p, cols->d_slid.p, cols->nlids,       \
+                     A->d_ekey.p, A->d_eidx.p, A->n_entries, absent_zero ? 1 : 0, vidx, bad.p)
+  if (global) {
+    PA_ENTRY_IDS(true, int64_t);
+  } else if (index_bytes == 8) {
+    PA_ENTRY_IDS(false, int64_t);
+  } else {
+    PA_ENTRY_IDS(false, int32_t);
+  }
+#undef PA_ENTRY_IDS
+  PA_HIP_OR(hipGetLastError(), -1);
+  PA_HIP_OR(hipMemcpyAsync(hbad, bad, 2 * sizeof(int), hipMemcpyDeviceToHost, st), -1);
+  PA_HIP_OR(hipStreamSynchronize(st), -1);
+  if (hbad[0]) return 1;
+  return (stored && hbad[1]) ? 2 : 0;
 }
 
 }  // namespace pa

@@ -720,6 +720,21 @@ struct pa_mat {
   pa::TripleSell tri;
   pa::UniformRows uni;
   pa::DevBuf<void> d_dotp;  // fused dot: one partial per (main + side + triple) slice and long row
+
+  // Entry views (pa_mat_scatter / pa_mat_gather).  The
+  // builders that set nz_map keep the (row lid, col lid) of each ghost-row
+  // nonzero (0-based, in the order of their values after the slots; a pair
+  // of -1: an index out of range in a ghost row of a CSR parent), n_gnz * 8 B:
+  // the only thing a matrix that never opens a view carries for them.  The
+  // entry table is built by the first view call (mat_entry_table): the keys
+  // row_lid * ncols_lids + col_lid of the stored entries, ascending, and each
+  // entry's value index in main.val.
+  int64_t nrows_lids = 0;
+  pa::DevBuf<int32_t> d_ghost_rc;    // 2 * n_gnz
+  bool has_entries = false;
+  int64_t n_entries = 0;
+  pa::DevBuf<uint64_t> d_ekey;       // n_entries
+  pa::DevBuf<int64_t> d_eidx;        // n_entries
 };
 
 namespace pa {
@@ -737,4 +752,17 @@ inline int64_t dot_base(const pa_mat* A, SliceKind k) {
 inline int64_t long_dot_base(const pa_mat* A) {
   return pattern_layout(A) ? dot_base(A, kTriple) + A->tri.nslices : A->main.nslices;
 }
+
+// The entry views of a matrix (pa_coo.hip; pa_mat_scatter / pa_mat_gather).
+// mat_entry_table builds A's entry table from its layout (rows: the index
+// set of the matrix's rows); 0, or -1 on a HIP error.  mat_entry_ids writes
+// the 1-based value index in main.val of each (I[k], J[k]) to vidx (0: no
+// such value) — I, J, vidx device arrays, ids as in pa::vec_scatter, looked
+// up in rows / cols — and returns 1 when an id has no lid (absent_zero: an
+// absent global id is no error), 2 when `stored` and a valid (i, j) is not
+// stored, -1 on a HIP error.  Both have completed on st when they return.
+int mat_entry_table(pa_mat* A, const pa_index* rows, hipStream_t st);
+int mat_entry_ids(const pa_mat* A, const pa_index* rows, const pa_index* cols, bool global, int index_bytes,
+                  bool absent_zero, bool stored, int64_t n, const void* I, const void* J, int64_t* vidx,
+                  hipStream_t st);
 }  // namespace pa

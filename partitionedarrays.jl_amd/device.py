@@ -461,6 +461,28 @@ def _ids_arg(ids, ids_global, writable):
     return b.size, b.dtype.itemsize, False, b.ctypes.data_as(C.c_void_p), keep
 
 
+def _ids_pair(I, J, ids_global):
+    """(n, index_bytes, on_device, pointer of I, pointer of J, keep) of the
+    row and column ids of a matrix access: both cross in one width (Int32
+    only when both are Int32 lids).  keep holds the host copies alive."""
+    if isinstance(I, DeviceArray) != isinstance(J, DeviceArray):
+        raise TypeError("I and J must both be host arrays or both DeviceArray")
+    if isinstance(I, DeviceArray):
+        if I.dtype != J.dtype or I.n != J.n:
+            raise ValueError("I and J on the device must have one type and one length")
+        n, ib, _, ip, _ = _ids_arg(I, ids_global, writable=False)
+        return n, ib, True, ip, C.c_void_p(J.ptr), None
+    a, b = np.asarray(I), np.asarray(J)
+    if (a.size and a.dtype.kind not in "iu") or (b.size and b.dtype.kind not in "iu"):
+        raise TypeError("ids must be integers")
+    want = np.int32 if (not ids_global and a.dtype == np.int32 and b.dtype == np.int32) else np.int64
+    a = np.ascontiguousarray(a, dtype=want).ravel()
+    b = np.ascontiguousarray(b, dtype=want).ravel()
+    if a.size != b.size:
+        raise ValueError("I and J must have the same length")
+    return a.size, a.dtype.itemsize, False, a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), (a, b)
+
+
 class DeviceCOO:
     """pa_coo: the COO triplets (I, J global ids, V) of one part in HBM."""
 
@@ -621,6 +643,56 @@ class DeviceMatrix:
         a = np.empty(n, dtype=self.dtype)
         _lib.call("pa_mat_get_values", self.h, a.ctypes.data_as(C.c_void_p))
         return a
+
+    def scatter(self, rows_idx: DeviceIndex, cols_idx: DeviceIndex, I, J, V, ids_global=False,
+                op=_lib.PA_SCATTER_ADD):
+        """pa_mat_scatter: a[I[k], J[k]] += V[k] (or = with PA_SCATTER_SET) in
+        input order over the stored entries, then the SpMV layouts' copies of
+        the values are refreshed.  I, J: 1-based lids (Int32 / Int64) of the
+        matrix's rows / cols, or Int64 gids when ids_global; they are left
+        unchanged.  I, J, V: host arrays, or all DeviceArray.  A write to an
+        entry the pattern does not store is an error."""
+        n, ib, on_device, ip, jp, _keep = _ids_pair(I, J, ids_global)
+        if on_device != isinstance(V, DeviceArray):
+            raise TypeError("scatter: I, J and V must all be host arrays or all DeviceArray")
+        if on_device:
+            if V.dtype != self.dtype or V.n != n:
+                raise ValueError("scatter: V must hold one value of the matrix's type per entry")
+            vp = C.c_void_p(V.ptr)
+        else:
+            V = np.ascontiguousarray(V, dtype=self.dtype).ravel()
+            if len(V) != n:
+                raise ValueError("scatter: I, J and V must have the same length")
+            vp = V.ctypes.data_as(C.c_void_p)
+        _lib.call("pa_mat_scatter", self.h, rows_idx.h, cols_idx.h,
+                  _lib.PA_IDS_GLOBAL if ids_global else _lib.PA_IDS_LOCAL, ib, int(op), 1 if on_device else 0, n,
+                  ip, jp, vp)
+
+    def gather(self, rows_idx: DeviceIndex, cols_idx: DeviceIndex, I, J, ids_global=False, absent_zero=False,
+               out=None):
+        """pa_mat_gather: a[I[k], J[k]] as a host array (I, J host arrays), or
+        into the DeviceArray `out` (I, J DeviceArray).  An entry the pattern
+        does not store reads zero; an absent gid reads zero with absent_zero,
+        else it is an error."""
+        n, ib, on_device, ip, jp, _keep = _ids_pair(I, J, ids_global)
+        if on_device:
+            if not isinstance(out, DeviceArray) or out.dtype != self.dtype or out.n != n:
+                raise TypeError("gather: device ids need a DeviceArray `out` of the matrix's type, one value per entry")
+            op = C.c_void_p(out.ptr)
+        else:
+            out = np.empty(n, dtype=self.dtype)
+            op = out.ctypes.data_as(C.c_void_p)
+        _lib.call("pa_mat_gather", self.h, rows_idx.h, cols_idx.h,
+                  _lib.PA_IDS_GLOBAL if ids_global else _lib.PA_IDS_LOCAL, ib, 1 if absent_zero else 0,
+                  1 if on_device else 0, n, ip, jp, op)
+        return out
+
+    def entry_table(self):
+        """pa_mat_entry_info: (entries, bytes) of the entry table the first
+        scatter / gather builds; (0, 0) before."""
+        e, b = C.c_int64(), C.c_int64()
+        _lib.call("pa_mat_entry_info", self.h, C.byref(e), C.byref(b))
+        return e.value, b.value
 
     def cg_choice(self) -> int:
         """the device CG's remembered u-update variant (pa_mat_cg_choice:

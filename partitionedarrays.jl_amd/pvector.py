@@ -282,15 +282,44 @@ def _scatter_parts(v: PVector, I: PData, V: PData, ids, op, zero_first=False):
     return v
 
 
-def add_coo_(v: PVector, I: PData, V: PData, ids="global") -> PVector:
-    """The batched `view[I] .+= V` over global_view(v, v.rows) (ids="global")
-    or local_view(v, v.rows) (ids="local"): v[I[k]] += V[k] in input order on
-    every part, on the device (test_fem_sa.jl:86-101 as one call per part).
-    Int64 arrays of global ids are translated to lids in place, as in
-    PVector.from_coo."""
+def add_coo_(v, I: PData, *args, ids="global"):
+    """add_coo_(v, I, V, ids): the batched `view[I] .+= V` over
+    global_view(v, v.rows) (ids="global") or local_view(v, v.rows)
+    (ids="local"): v[I[k]] += V[k] in input order on every part, on the
+    device (test_fem_sa.jl:86-101 as one call per part).  Int64 arrays of
+    global ids are translated to lids in place, as in PVector.from_coo.
+
+    add_coo_(A, I, J, V, ids) for a PSparseMatrix A: `view[I, J] .+= V` over
+    global_view(A, A.rows, A.cols) / local_view(A, A.rows, A.cols), the
+    re-assembly loop of a fixed pattern (test_fem_sa.jl:74-84 after
+    fillstored!(A, 0)): A[I[k], J[k]] += V[k] over the stored entries in
+    input order, owned and ghost rows (pa_mat_scatter).  I and J stay as
+    they are; an (i, j) the pattern does not store is an error.  Returns its
+    first argument."""
+    nfix = 2 if isinstance(v, PSparseMatrix) else 1  # J, V or V; then ids may follow positionally
+    if len(args) == nfix + 1:
+        args, ids = args[:nfix], args[nfix]
+    if len(args) != nfix:
+        raise TypeError("add_coo_(v, I, V, ids) for a PVector, add_coo_(A, I, J, V, ids) for a PSparseMatrix")
     if ids not in ("global", "local"):
         raise ValueError("add_coo_: ids must be 'global' or 'local'")
-    return _scatter_parts(v, I, V, ids, _lib.PA_SCATTER_ADD)
+    if nfix == 1:
+        return _scatter_parts(v, I, args[0], ids, _lib.PA_SCATTER_ADD)
+    J, V = args
+    if any(x.part_ids != v.values.part_ids for x in (I, J, V)):
+        raise ValueError("add_coo_(A, I, J, V): partitioned data over different parts")
+    glob = ids == "global"
+    for M, (r, c), i, j, w in zip(v.values.parts, _mat_index(v, glob), I.parts, J.parts, V.parts):
+        M.scatter(r, c, i, j, w, ids_global=glob, op=_lib.PA_SCATTER_ADD)
+    return v
+
+
+def _mat_index(A, glob: bool):
+    """per part, the device index sets of A's rows and cols (with their gid
+    tables when glob)"""
+    mk = device_index_gids if glob else device_index
+    return [(mk(c, r), mk(c, s))
+            for c, r, s in zip(contexts(A.rows.partition), A.rows.partition.parts, A.cols.partition.parts)]
 
 
 class VectorView:
@@ -331,21 +360,94 @@ class VectorView:
         return self
 
 
-def global_view(v: PVector, rows: PRange = None) -> PData:
+class MatrixView:
+    """One part's GlobalView / LocalView of a PSparseMatrix (Interfaces.jl:
+    2277-2298 over 2004-2069) with batched access over the stored entries:
+    get(I, J) = view[I[k], J[k]], set_(I, J, V) = `view[i, j] = v` (a repeated
+    (i, j) keeps its last value), add_(I, J, V) = `view[i, j] += v` in input
+    order.  An (i, j) the pattern does not store reads zero(T) and cannot be
+    written (the reference would insert it; the device pattern is fixed).
+
+    kind "local": lids of the matrix's own rows and cols.  kind "global":
+    gids.  kind "mapped" (local_view over other ranges): lids of those
+    ranges, mapped to gids on the host (`rgids`, `cgids`: their lid_to_gid)
+    and looked up on the device; a lid the matrix's ranges do not hold reads
+    zero(T) (2019-2026) and cannot be written (2027-2031)."""
+
+    def __init__(self, M: DeviceMatrix, ridx, cidx, kind, rgids=None, cgids=None):
+        self.M, self.ridx, self.cidx, self.kind, self.rgids, self.cgids = M, ridx, cidx, kind, rgids, cgids
+
+    def _ids(self, ids, gids):
+        if self.kind != "mapped":
+            return ids
+        ids = np.asarray(ids).astype(np.int64).ravel()
+        if len(ids) and (ids.min() < 1 or ids.max() > len(gids)):
+            raise _lib.PAError("local_view: a local id is out of range (BoundsError)")
+        return gids[ids - 1]
+
+    def get(self, I, J):
+        return self.M.gather(self.ridx, self.cidx, self._ids(I, self.rgids), self._ids(J, self.cgids),
+                             ids_global=self.kind != "local", absent_zero=self.kind == "mapped")
+
+    def _write(self, I, J, V, op):
+        self.M.scatter(self.ridx, self.cidx, self._ids(I, self.rgids), self._ids(J, self.cgids), V,
+                       ids_global=self.kind != "local", op=op)
+        return self
+
+    def set_(self, I, J, V):
+        return self._write(I, J, V, _lib.PA_SCATTER_SET)
+
+    def add_(self, I, J, V):
+        return self._write(I, J, V, _lib.PA_SCATTER_ADD)
+
+
+def _mat_views(A, rows, cols, glob: bool):
+    p = A.values
+    own = (rows is None or rows is A.rows) and (cols is None or cols is A.cols)
+    if glob:
+        if not own:
+            raise NotImplementedError("global_view(a, rows, cols): only for rows === a.rows and cols === a.cols "
+                                      "(Interfaces.jl:2291-2292)")
+        views = [MatrixView(M, r, c, "global") for M, (r, c) in zip(p.parts, _mat_index(A, True))]
+    elif own:
+        views = [MatrixView(M, r, c, "local") for M, (r, c) in zip(p.parts, _mat_index(A, False))]
+    else:
+        rows, cols = A.rows if rows is None else rows, A.cols if cols is None else cols
+        if rows.partition.part_ids != p.part_ids or cols.partition.part_ids != p.part_ids:
+            raise ValueError("local_view: rows / cols over different parts")
+        views = [MatrixView(M, r, c, "mapped", np.asarray(s.lid_to_gid, dtype=np.int64),
+                            np.asarray(t.lid_to_gid, dtype=np.int64))
+                 for M, (r, c), s, t in zip(p.parts, _mat_index(A, True), rows.partition.parts, cols.partition.parts)]
+    return PData(p.backend, p.part_ids, views, p.shape)
+
+
+def global_view(v, rows: PRange = None, cols: PRange = None) -> PData:
     """global_view(a, rows) (Interfaces.jl:2037-2043): per part, the values
-    indexed by global ids; only over the vector's own rows (2038)."""
+    indexed by global ids; only over the vector's own rows (2038).
+    global_view(A, rows, cols) for a PSparseMatrix (2290-2298): MatrixView
+    per part, only over the matrix's own rows and cols."""
+    if isinstance(v, PSparseMatrix):
+        return _mat_views(v, rows, cols, True)
+    if cols is not None:
+        raise TypeError("global_view(a, rows): a PVector has no cols")
     if rows is not None and rows is not v.rows:
         raise NotImplementedError("global_view(a, rows): only for rows === a.rows (Interfaces.jl:2038)")
     views = [VectorView(dv, x, "global") for dv, x in zip(v.values.parts, _part_index(v, True))]
     return PData(v.values.backend, v.values.part_ids, views, v.values.shape)
 
 
-def local_view(v: PVector, rows: PRange = None) -> PData:
+def local_view(v, rows: PRange = None, cols: PRange = None) -> PData:
     """local_view(a, rows) (Interfaces.jl:1994-2002): per part, the values
     indexed by the local ids of rows.  Over the vector's own rows these are
     its lids; over another range each lid is mapped to its gid on the host
     (find_lid_map's role) and looked up in the vector's gid table on the
-    device."""
+    device.  local_view(A, rows, cols) for a PSparseMatrix (2277-2288):
+    MatrixView per part, over the matrix's own ranges or, mapped the same
+    way, over others."""
+    if isinstance(v, PSparseMatrix):
+        return _mat_views(v, rows, cols, False)
+    if cols is not None:
+        raise TypeError("local_view(a, rows): a PVector has no cols")
     p = v.values
     if rows is None or rows is v.rows:
         views = [VectorView(dv, x, "local") for dv, x in zip(p.parts, _part_index(v, False))]
