@@ -249,6 +249,12 @@ int pa_add_gids(pa_index* idx, int64_t n, const int64_t* gids, int64_t cap,
  * (Interfaces.jl:723-786) uses it for lids_snd of the gids its receivers
  * asked for.                                                              */
 int pa_index_to_lids(pa_index* idx, int64_t n, int64_t* ids);
+/* to_gids!(ids, a) (Interfaces.jl:638-645, 1545-1547), the mirror of
+ * pa_index_to_lids: the n 1-based lids in ids become 1-based gids, in place,
+ * through the lid_to_gid that pa_index_set_gids attached (kept on the device,
+ * 8 B per lid).  A lid outside 1..num_lids fails (BoundsError) and nothing
+ * is written.                                                             */
+int pa_index_to_gids(pa_index* idx, int64_t n, int64_t* ids);
 
 /* ---- vectors (the values of one part of a PVector) --------------------- */
 int pa_vec_create(pa_ctx* ctx, int dtype, int64_t n, pa_vec** out);
@@ -582,6 +588,36 @@ int pa_mat_gather(const pa_mat* A, pa_index* rows, pa_index* cols, int ids_kind,
  * owned-row nonzeros + its ghost-row nonzeros), 0 while no view call has
  * built it; *bytes = the device memory it takes.                          */
 int pa_mat_entry_info(const pa_mat* A, int64_t* entries, int64_t* bytes);
+/* findnz(A) / nziterator(A) of one part on the device (SparseUtils.jl:
+ * 106-150, 254-300): the stored entries as a new device COO, the inverse of
+ * pa_mat_from_dcoo and the first step of gather(A) (Interfaces.jl:2664-2704).
+ * I and J are 1-based Int64: lids (PA_IDS_LOCAL), or gids through the
+ * lid_to_gid of rows / cols (PA_IDS_GLOBAL: needs pa_index_set_gids).  V has
+ * the matrix's dtype, one value per entry read from the main value array (the
+ * copy every SpMV layout is refreshed from).  The COO owns its buffers
+ * (pa_coo_destroy); A is unchanged.
+ * which_rows: PA_NZ_OWNED_ROWS keeps the entries of the rows this part owns,
+ * `rows.lid_to_part[i] == rows.part`, the filter of Interfaces.jl:2671-2687
+ * (SELL slots, side rows and long rows alike); PA_NZ_ALL_ROWS adds the stored
+ * ghost rows.
+ * Order: the parent's nziterator order — ascending (col lid, row lid) for a
+ * CSC parent, ascending (row lid, col lid) for a CSR parent, ghost rows in
+ * their place.  Deviation: a pa_mat_from_csr parent whose rows are not
+ * column-sorted gives every stored entry exactly once in ascending (row, col),
+ * not in its storage order (the device keeps no copy of the parent's colval;
+ * DESIGN.md 4.9).  Padding slots give nothing.
+ * Route: the entry table's emit / compact / sort passes with the parent's
+ * key, on pairs of the call's own — the matrix's entry table is neither read
+ * nor built (pa_mat_entry_info is unchanged by the call).  All counts are
+ * 64-bit.  The call runs on the part's compute stream and has completed on
+ * it when it returns.  rows and cols must be the index sets the matrix was
+ * built with; a pa_mat_stencil matrix has no nonzero map and fails with a
+ * message, as the entry views do.  Bad arguments fail before anything is
+ * allocated.                                                              */
+#define PA_NZ_OWNED_ROWS 0
+#define PA_NZ_ALL_ROWS 1
+int pa_mat_findnz(pa_mat* A, pa_index* rows, pa_index* cols, int which_rows, int ids_kind,
+                  pa_coo** out);
 /* matrix_exchanger(values, rows, cols) (Interfaces.jl:2300-2372): the
  * Exchanger whose lids are CSC nz positions k (1-based, Int64 as Julia's
  * Table{Int}): k_rcv = nonzeros of ghost rows grouped by owner, k_snd = the

@@ -835,6 +835,64 @@ function view_get(a::HIPMatrix{T}, I::HIPData, J::HIPData; ids::Symbol, absent_z
   HIPData(out, a.values.ctxs, a.values.backend)
 end
 
+# ---- findnz on the device, to_gids! and gather(A) (Interfaces.jl:2664-2704) -
+# pa_mat_findnz reads a part's stored entries back in the parent's nziterator
+# order (the loop of 2669-2689 with its owned-row filter); gather(A) below is
+# the reference's method with that loop replaced, so A \ b, lu, lu! and ldiv!
+# (2626-2662) take the matrix from the device without a host copy of nzval.
+const PA_NZ_OWNED_ROWS, PA_NZ_ALL_ROWS = Cint(0), Cint(1)
+
+"""(I, J, V) of the stored entries of every part: `rows = :owned` the rows the
+part owns, `:all` the stored ghost rows too; `ids = :global` gids, `:local`
+lids of a.rows / a.cols."""
+function dev_findnz(a::HIPMatrix{T}; rows::Symbol=:owned, ids::Symbol=:global) where {T<:DeviceEltype}
+  @assert rows in (:owned, :all) && ids in (:global, :local)
+  hs = dev_mat(a)
+  rh, ch = _mat_view_idx(a.rows, ids), _mat_view_idx(a.cols, ids)
+  out = map(eachindex(a.values.parts)) do i
+    coo = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:pa_mat_findnz, libpa), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Ref{Ptr{Cvoid}}),
+                hs[i], rh[i], ch[i], rows === :all ? PA_NZ_ALL_ROWS : PA_NZ_OWNED_ROWS, _ids_kind(ids), coo))
+    try
+      m = Ref{Int64}(0)
+      check(ccall((:pa_coo_size, libpa), Cint, (Ptr{Cvoid}, Ref{Int64}), coo[], m))
+      I = Vector{Int64}(undef, m[]); J = Vector{Int64}(undef, m[]); V = Vector{T}(undef, m[])
+      check(ccall((:pa_coo_download, libpa), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{T}),
+                  coo[], I, J, V))
+      (I, J, V)
+    finally
+      ccall((:pa_coo_destroy, libpa), Cint, (Ptr{Cvoid},), coo[])
+    end
+  end
+  ntuple(k -> HIPData([o[k] for o in out], a.values.ctxs, a.values.backend), 3)
+end
+
+function PartitionedArrays.to_gids!(I::HIPData{<:Vector{Int64}}, a::PRange)
+  for i in eachindex(I.parts)
+    h = _idx_gids_handle(a.partition.ctxs[i], a.partition.parts[i])
+    check(ccall((:pa_index_to_gids, libpa), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}),
+                h, length(I.parts[i]), I.parts[i]))
+  end
+  I
+end
+
+function PartitionedArrays.gather(a::HIPMatrix{T},
+                                  rows_in_main::PRange=PartitionedArrays._to_main(a.rows),
+                                  cols_in_main::PRange=PartitionedArrays._to_main(a.cols)) where {T<:DeviceEltype}
+  I, J, V = dev_findnz(a; rows=:owned, ids=:global)
+  assemble!(I, J, V, rows_in_main)
+  for i in eachindex(I.parts)
+    if a.rows.partition.parts[i].part != MAIN
+      resize!(I.parts[i], 0); resize!(J.parts[i], 0); resize!(V.parts[i], 0)
+    end
+  end
+  M = eltype(a.values)
+  exchanger = PartitionedArrays.empty_exchanger(rows_in_main.partition)
+  PSparseMatrix((args...) -> PartitionedArrays.compresscoo(M, args...),
+                I, J, V, rows_in_main, cols_in_main, exchanger; ids=:global)
+end
+
 # ---- reductions (Interfaces.jl:221-238, 1767-1772, 1973-1992) -------------
 function LinearAlgebra.dot(a::HIPVector{T}, b::HIPVector{T}) where {T<:DeviceEltype}
   r = Ref{T}(zero(T))

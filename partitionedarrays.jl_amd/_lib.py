@@ -21,6 +21,7 @@ TUNE_DROP = -(2 ** 31)  # pa_ctx_tune: drop a context's override (PA_TUNE_DROP)
 PA_BCAST_F64, PA_BCAST_C128 = 8, 16  # pa_vec_axpby scalar kinds (Float64 / ComplexF64 scalars)
 PA_IDS_LOCAL, PA_IDS_GLOBAL = 0, 1  # pa_vec_scatter / pa_vec_gather: 1-based lids, or Int64 gids
 PA_SCATTER_ADD, PA_SCATTER_SET = 0, 1
+PA_NZ_OWNED_ROWS, PA_NZ_ALL_ROWS = 0, 1  # pa_mat_findnz: the owned rows' entries, or the stored ghost rows' too
 
 # broadcast expressions (pa_expr of include/pa_hip.h)
 EXPR_MAX_OPS, EXPR_MAX_VECS, EXPR_MAX_SCALARS, EXPR_MAX_DEPTH = 32, 8, 8, 4
@@ -112,6 +113,8 @@ _SIGS = {
     "pa_index_set_gids": [_p, _i64p],
     "pa_add_gids": [_p, C.c_int64, _i64p, C.c_int64, _i64p, _i64p],
     "pa_index_to_lids": [_p, C.c_int64, _i64p],
+    "pa_index_to_gids": [_p, C.c_int64, _i64p],
+    "pa_mat_findnz": [_p, _p, _p, C.c_int, C.c_int, C.POINTER(_p)],
     "pa_mat_set_values": [_p, _p],
     "pa_mat_get_values": [_p, _p],
     "pa_mat_scatter": [_p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, _p, _p, _p],

@@ -112,6 +112,7 @@ void launch_spmv_long(const pa_mat* A, const void* x, void* y, const int32_t* ym
                       const void* alpha, const void* beta, void* dotp, int64_t dot_base, hipStream_t st);
 int gid_table(int64_t n, const int64_t* d_lid_to_gid, DevBuf<uint64_t>& sgid, DevBuf<int64_t>& slid, hipStream_t st);
 int gids_to_lids(int64_t n, int64_t* ids, const uint64_t* sgid, const int64_t* slid, int64_t nl, hipStream_t st);
+int lids_to_gids(int64_t n, int64_t* ids, const int64_t* l2g, int64_t nl, hipStream_t st);
 int coo_send_pack(bool to_ghosts, int dtype, const CooList& in, const uint64_t* sgid, const int64_t* slid, int64_t nl,
                   const std::vector<int32_t>& lid_to_ohid, const XchgSide& side, CooList* out,
                   std::vector<int64_t>* cnt, hipStream_t st);
@@ -2036,12 +2037,14 @@ int pa_index_set_gids(pa_index* I, const int64_t* lid_to_gid) {
   HIPC(hipSetDevice(c->device));
   I->d_sgid.reset();
   I->d_slid.reset();
+  I->d_lid_to_gid.reset();
   if (I->nlids > 0) {
     std::vector<int64_t> h(lid_to_gid, lid_to_gid + I->nlids);
     for (int64_t g : h) CHECK_ARG(g >= 1, "lid_to_gid: gids are 1-based");
     DevBuf<int64_t> d;
     HIPC(d.upload(h));
     CHECK_ARG(gid_table(I->nlids, d, I->d_sgid, I->d_slid, c->s_main) == 0, "pa_index_set_gids: device sort failed");
+    I->d_lid_to_gid = std::move(d);  // the forward map (pa_index_to_gids, pa_mat_findnz)
   }
   I->has_gids = true;
   return 0;
@@ -2085,6 +2088,26 @@ int pa_index_to_lids(pa_index* I, int64_t n, int64_t* ids) {
   const int rc = gids_to_lids(n, d, I->d_sgid, I->d_slid, I->nlids, c->s_main);
   CHECK_ARG(rc >= 0, "pa_index_to_lids: device pass failed");
   CHECK_ARG(rc == 0, "to_lids!: a global id is not a local id of the part (KeyError)");
+  HIPC(hipStreamSynchronize(c->s_main));  // (hipMemcpy runs on the null stream)
+  HIPC(hipMemcpy(ids, d, n * 8, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// to_gids!(ids, a) (Interfaces.jl:638-645, 1545-1547): the twin of
+// pa_index_to_lids through the forward map; ids is written only on success
+int pa_index_to_gids(pa_index* I, int64_t n, int64_t* ids) {
+  CHECK_ARG(I && (n == 0 || ids), "null argument");
+  CHECK_ARG(n >= 0, "pa_index_to_gids: negative length");
+  CHECK_ARG(I->has_gids, "pa_index_to_gids: call pa_index_set_gids first");
+  pa_ctx* c = I->ctx;
+  HIPC(hipSetDevice(c->device));
+  if (n == 0) return 0;
+  DevBuf<int64_t> d;
+  HIPC(d.alloc(n));
+  HIPC(hipMemcpy(d, ids, n * 8, hipMemcpyHostToDevice));
+  const int rc = lids_to_gids(n, d, I->d_lid_to_gid, I->nlids, c->s_main);
+  CHECK_ARG(rc >= 0, "pa_index_to_gids: device pass failed");
+  CHECK_ARG(rc == 0, "to_gids!: a local id is out of range (BoundsError)");
   HIPC(hipStreamSynchronize(c->s_main));  // (hipMemcpy runs on the null stream)
   HIPC(hipMemcpy(ids, d, n * 8, hipMemcpyDeviceToHost));
   return 0;
@@ -3242,6 +3265,30 @@ int pa_mat_gather(const pa_mat* A, pa_index* rows, pa_index* cols, int ids_kind,
     HIPC(hipMemcpyAsync(out, dO, obytes, hipMemcpyDeviceToHost, c->s_main));
     HIPC(hipStreamSynchronize(c->s_main));
   }
+  return 0;
+}
+
+// findnz(A) / nziterator(A) of one part as a new device COO (pa_coo.hip,
+// mat_findnz): the first step of gather(A) (Interfaces.jl:2669-2689)
+int pa_mat_findnz(pa_mat* A, pa_index* rows, pa_index* cols, int which_rows, int ids_kind, pa_coo** out) {
+  const std::string w = "pa_mat_findnz: ";
+  CHECK_ARG(which_rows == PA_NZ_OWNED_ROWS || which_rows == PA_NZ_ALL_ROWS,
+            w + "which_rows must be PA_NZ_OWNED_ROWS or PA_NZ_ALL_ROWS");
+  CHECK_ARG(ids_kind == PA_IDS_LOCAL || ids_kind == PA_IDS_GLOBAL, w + "ids_kind must be PA_IDS_LOCAL or PA_IDS_GLOBAL");
+  CHECK_ARG(A && rows && cols && out, w + "null argument");
+  CHECK_ARG(A->ctx == rows->ctx && A->ctx == cols->ctx, w + "the matrix and the index sets belong to different parts");
+  CHECK_ARG(A->nz_map, w + "matrix was not built from a CSC pattern");
+  CHECK_ARG(rows->nlids == A->nrows_lids && rows->noids == A->main.nrows && cols->nlids == A->ncols_lids,
+            w + "the index sets do not have the matrix's local ids");
+  CHECK_ARG(ids_kind != PA_IDS_GLOBAL || (rows->has_gids && cols->has_gids), w + "call pa_index_set_gids first");
+  pa_ctx* c = A->ctx;
+  HIPC(hipSetDevice(c->device));
+  auto C = std::make_unique<pa_coo>();
+  C->ctx = c;
+  C->dtype = A->dtype;
+  CHECK_ARG(mat_findnz(A, rows, cols, which_rows == PA_NZ_OWNED_ROWS, ids_kind == PA_IDS_GLOBAL, C->l, c->s_main) == 0,
+            w + "device pass failed");
+  *out = C.release();
   return 0;
 }
 

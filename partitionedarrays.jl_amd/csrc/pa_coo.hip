@@ -506,6 +506,31 @@ int gids_to_lids(int64_t n, int64_t* ids, const uint64_t* sgid, const int64_t* s
   return hbad ? 1 : 0;
 }
 
+// ids (1-based lids) → 1-based gids in place through lid_to_gid (nl entries);
+// *bad = 1 if a lid is outside 1..nl (that id is left as it was)
+__global__ void k_to_gids(int64_t n, int64_t* __restrict__ ids, const int64_t* __restrict__ l2g, int64_t nl,
+                          int* __restrict__ bad) {
+  for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t l = ids[k];
+    if (l < 1 || l > nl) *bad = 1;
+    else ids[k] = l2g[l - 1];
+  }
+}
+
+// ids (n, device, 1-based lids) → 1-based gids; returns 1 if a lid is out of range
+int lids_to_gids(int64_t n, int64_t* ids, const int64_t* l2g, int64_t nl, hipStream_t st) {
+  if (n <= 0) return 0;
+  DevBuf<int> bad;
+  int hbad = 0;
+  PA_HIP_OR(bad.alloc(1), -1);
+  PA_HIP_OR(hipMemsetAsync(bad, 0, sizeof(int), st), -1);
+  hipLaunchKernelGGL(k_to_gids, grid1(n), dim3(256), 0, st, n, ids, l2g, nl, bad.p);
+  PA_HIP_OR(hipGetLastError(), -1);
+  PA_HIP_OR(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, st), -1);
+  PA_HIP_OR(hipStreamSynchronize(st), -1);
+  return hbad ? 1 : 0;
+}
+
 // add_gids!: the gids (device, n) absent from the table, each once, in order
 // of first occurrence: out (device, *m_out entries)
 int gids_first_touch(int64_t n, const int64_t* gids, const uint64_t* sgid, const int64_t* slid, int64_t nl,
@@ -979,6 +1004,10 @@ struct EntrySrc {
   const int32_t* long_row;
   const int64_t* long_ptr;
   const int32_t* long_col;
+  // pa_mat_findnz (zero for the entry table): column-major keys
+  // col_lid * nrl + row_lid, and the stored ghost rows left out
+  int64_t nrl;
+  int colmajor, owned_only;
 };
 
 // value index t of main.val: flag[t] = 1 and key[t] = its entry's key when
@@ -1004,8 +1033,10 @@ __global__ void k_entry_emit(EntrySrc a, uint64_t* __restrict__ key, int64_t* __
       if (oid < a.nrows && c >= 0) r = a.oid_to_lid ? a.oid_to_lid[oid] : oid;
     } else if (t < a.slots + a.n_gnz) {
       const int64_t g = t - a.slots;
-      r = a.grc[2 * g];
-      c = a.grc[2 * g + 1];
+      if (!a.owned_only) {
+        r = a.grc[2 * g];
+        c = a.grc[2 * g + 1];
+      }
     } else {
       const int64_t q = t - a.slots - a.n_gnz;
       int64_t lo = 0, hi = a.n_long;  // the long row whose CSR range holds q
@@ -1019,7 +1050,9 @@ __global__ void k_entry_emit(EntrySrc a, uint64_t* __restrict__ key, int64_t* __
     }
     const bool ok = r >= 0 && c >= 0;
     flag[t] = ok ? 1 : 0;
-    key[t] = ok ? (uint64_t)r * (uint64_t)a.ncols + (uint64_t)c : 0;
+    key[t] = !ok ? 0
+             : a.colmajor ? (uint64_t)c * (uint64_t)a.nrl + (uint64_t)r
+                          : (uint64_t)r * (uint64_t)a.ncols + (uint64_t)c;
   }
 }
 
@@ -1077,7 +1110,7 @@ int mat_entry_table(pa_mat* A, const pa_index* rows, hipStream_t st) {
     PA_HIP_OR(rank.alloc(nv), -1);
     const EntrySrc a = {A->main.slots, A->n_gnz, A->n_lnz, A->main.nrows, A->main.nslices, A->ncols_lids, A->n_long,
                         A->H, A->R, A->main.off, A->main.col, A->d_kind, rows->own_contig ? nullptr : rows->d_oid_to_lid.p,
-                        A->d_ghost_rc, A->d_long_row, A->d_long_ptr, A->d_long_col};
+                        A->d_ghost_rc, A->d_long_row, A->d_long_ptr, A->d_long_col, 0, 0, 0};
     hipLaunchKernelGGL(k_entry_emit, grid1(nv), dim3(256), 0, st, a, key.p, flag.p);
     PA_HIP_OR(hipGetLastError(), -1);
     PA_HIP_OR(exclusive_sum(flag, rank, nv, st), -1);
@@ -1127,6 +1160,101 @@ int mat_entry_ids(const pa_mat* A, const pa_index* rows, const pa_index* cols, b
   PA_HIP_OR(hipStreamSynchronize(st), -1);
   if (hbad[0]) return 1;
   return (stored && hbad[1]) ? 2 : 0;
+}
+
+// ---------------------------------------------------------------------------
+// findnz / nziterator of a PSparseMatrix part (pa_mat_findnz; the filter of
+// gather(A), Interfaces.jl:2671-2687): the stored entries back as (I, J, V)
+// in the parent's storage order, the inverse of pa_mat_from_dcoo.  The entry
+// table's passes with the key of the parent's order — col_lid * nrows_lids +
+// row_lid for a CSC parent (SparseUtils.jl:106-150), row_lid * ncols_lids +
+// col_lid for a CSR parent (254-300) — emit, compact and sort the (key, value
+// index) pairs; k_findnz_write then splits each key into its ids and reads
+// the entry's value from main.val, the one copy every layout is refreshed
+// from.  The pairs are the call's own: the matrix's entry table is neither
+// used nor built.
+
+constexpr int kFindnzBlocks = 2048;  // grid of k_findnz_write (8 blocks per CU): kFindnzBlocks * 256 entries per grid pass
+
+// entry k of the sorted pairs: I[k], J[k] = its ids (1-based lids, or gids
+// through r2g / c2g), V[k] = val[eidx[k]].  Consecutive lanes write
+// consecutive entries of I, J and V; the value reads are gathers.
+template <typename T>
+__global__ __launch_bounds__(256) void k_findnz_write(int64_t ne, const uint64_t* __restrict__ key,
+                                                      const int64_t* __restrict__ eidx, uint64_t div, int colmajor,
+                                                      const int64_t* __restrict__ r2g, const int64_t* __restrict__ c2g,
+                                                      const T* __restrict__ val, int64_t* __restrict__ I,
+                                                      int64_t* __restrict__ J, T* __restrict__ V) {
+  for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < ne; k += (int64_t)gridDim.x * blockDim.x) {
+    const uint64_t q = key[k];
+    const uint64_t hi = q / div, lo = q - hi * div;
+    const int64_t r = (int64_t)(colmajor ? lo : hi), c = (int64_t)(colmajor ? hi : lo);
+    const T v = val[eidx[k]];
+    I[k] = r2g ? r2g[r] : r + 1;
+    J[k] = c2g ? c2g[c] : c + 1;
+    V[k] = v;
+  }
+}
+
+template <typename T>
+static void findnz_write_t(int64_t ne, const uint64_t* key, const int64_t* eidx, uint64_t div, int colmajor,
+                           const int64_t* r2g, const int64_t* c2g, const void* val, CooList& out, hipStream_t st) {
+  int64_t g = (ne + 255) / 256;
+  if (g > kFindnzBlocks) g = kFindnzBlocks;
+  hipLaunchKernelGGL(k_findnz_write<T>, dim3((unsigned)g), dim3(256), 0, st, ne, key, eidx, div, colmajor, r2g, c2g,
+                     (const T*)val, out.I.p, out.J.p, (T*)out.V.p);
+}
+
+int mat_findnz(const pa_mat* A, const pa_index* rows, const pa_index* cols, bool owned_only, bool global,
+               CooList& out, hipStream_t st) {
+  out.I.reset(), out.J.reset(), out.V.reset();
+  out.n = 0;
+  const int64_t nv = A->main.slots + A->n_gnz + A->n_lnz;
+  if (nv <= 0) return 0;
+  const int colmajor = A->csr ? 0 : 1;
+  DevBuf<uint64_t> key, ekey;
+  DevBuf<int64_t> flag, rank, eidx;
+  int64_t last[2] = {0, 0};
+  PA_HIP_OR(key.alloc(nv), -1);
+  PA_HIP_OR(flag.alloc(nv), -1);
+  PA_HIP_OR(rank.alloc(nv), -1);
+  const EntrySrc a = {A->main.slots, A->n_gnz, A->n_lnz, A->main.nrows, A->main.nslices, A->ncols_lids, A->n_long,
+                      A->H, A->R, A->main.off, A->main.col, A->d_kind, rows->own_contig ? nullptr : rows->d_oid_to_lid.p,
+                      A->d_ghost_rc, A->d_long_row, A->d_long_ptr, A->d_long_col, A->nrows_lids, colmajor,
+                      owned_only ? 1 : 0};
+  hipLaunchKernelGGL(k_entry_emit, grid1(nv), dim3(256), 0, st, a, key.p, flag.p);
+  PA_HIP_OR(hipGetLastError(), -1);
+  PA_HIP_OR(exclusive_sum(flag, rank, nv, st), -1);
+  PA_HIP_OR(hipMemcpyAsync(&last[0], rank.p + nv - 1, 8, hipMemcpyDeviceToHost, st), -1);
+  PA_HIP_OR(hipMemcpyAsync(&last[1], flag.p + nv - 1, 8, hipMemcpyDeviceToHost, st), -1);
+  PA_HIP_OR(hipStreamSynchronize(st), -1);
+  const int64_t ne = last[0] + last[1];
+  if (ne <= 0) return 0;
+  PA_HIP_OR(ekey.alloc(ne), -1);
+  PA_HIP_OR(eidx.alloc(ne), -1);
+  hipLaunchKernelGGL(k_entry_compact, grid1(nv), dim3(256), 0, st, nv, key.p, flag.p, rank.p, ekey.p, eidx.p);
+  PA_HIP_OR(hipGetLastError(), -1);
+  PA_HIP_OR(hipStreamSynchronize(st), -1);
+  key.reset(), flag.reset(), rank.reset();  // before the sort takes its buffers
+  const uint64_t nrl = (uint64_t)(A->nrows_lids > 0 ? A->nrows_lids : 1);
+  const uint64_t ncl = (uint64_t)(A->ncols_lids > 0 ? A->ncols_lids : 1);
+  PA_HIP_OR(sort_pairs(ekey, eidx, ne, bits_for(nrl * ncl), st), -1);
+  PA_HIP_OR(out.I.alloc(ne), -1);
+  PA_HIP_OR(out.J.alloc(ne), -1);
+  PA_HIP_OR(out.V.alloc(ne * dtype_size(A->dtype)), -1);
+  const int64_t* r2g = global ? rows->d_lid_to_gid.p : nullptr;
+  const int64_t* c2g = global ? cols->d_lid_to_gid.p : nullptr;
+  const uint64_t div = colmajor ? nrl : ncl;
+  switch (A->dtype) {
+    case PA_F32: findnz_write_t<float>(ne, ekey, eidx, div, colmajor, r2g, c2g, A->main.val, out, st); break;
+    case PA_F64: findnz_write_t<double>(ne, ekey, eidx, div, colmajor, r2g, c2g, A->main.val, out, st); break;
+    case PA_C64: findnz_write_t<c64>(ne, ekey, eidx, div, colmajor, r2g, c2g, A->main.val, out, st); break;
+    case PA_C128: findnz_write_t<c128>(ne, ekey, eidx, div, colmajor, r2g, c2g, A->main.val, out, st); break;
+  }
+  PA_HIP_OR(hipGetLastError(), -1);
+  PA_HIP_OR(hipStreamSynchronize(st), -1);
+  out.n = ne;
+  return 0;
 }
 
 }  // namespace pa

@@ -481,6 +481,7 @@ struct pa_index {
   // gid → lid table (pa_index_set_gids): gids sorted ascending, their lids
   pa::DevBuf<uint64_t> d_sgid;
   pa::DevBuf<int64_t> d_slid;
+  pa::DevBuf<int64_t> d_lid_to_gid;  // nlids 1-based gids (to_gids!, pa_mat_findnz with global ids)
   bool has_gids = false;
 };
 
@@ -765,4 +766,10 @@ int mat_entry_table(pa_mat* A, const pa_index* rows, hipStream_t st);
 int mat_entry_ids(const pa_mat* A, const pa_index* rows, const pa_index* cols, bool global, int index_bytes,
                   bool absent_zero, bool stored, int64_t n, const void* I, const void* J, int64_t* vidx,
                   hipStream_t st);
+// pa_mat_findnz (pa_coo.hip): the stored entries of A — of its owned rows, or
+// of every stored row — into out in the parent's storage order, ids as
+// 1-based lids or (global) gids through the lid_to_gid of rows / cols; 0, or
+// -1 on a HIP error.  The work has completed on st when it returns.
+int mat_findnz(const pa_mat* A, const pa_index* rows, const pa_index* cols, bool owned_only, bool global,
+               CooList& out, hipStream_t st);
 }  // namespace pa

@@ -298,6 +298,14 @@ def device_to_lids(ctx: PartContext, s, gids):
     return ids
 
 
+def device_to_gids(ctx: PartContext, s, lids):
+    """to_gids!(lids, s) through the device's lid_to_gid (pa_index_to_gids)."""
+    d = device_index_gids(ctx, s)
+    ids = np.array(lids, dtype=np.int64).ravel()
+    _lib.call("pa_index_to_gids", d.h, len(ids), ids.ctypes.data_as(C.POINTER(C.c_int64)))
+    return ids
+
+
 class DeviceExchanger:
     def __init__(self, ctx: PartContext, parts_rcv, lids_rcv, parts_snd, lids_snd):
         pr, prp = _lib.i32(parts_rcv)
@@ -499,6 +507,13 @@ class DeviceCOO:
                   J.ctypes.data_as(C.POINTER(C.c_int64)), V.ctypes.data_as(C.c_void_p), C.byref(h))
         self.h = h
 
+    @staticmethod
+    def _adopt(ctx: PartContext, dtype, h) -> "DeviceCOO":
+        """the owner of a pa_coo the library returned (pa_mat_findnz)"""
+        coo = DeviceCOO.__new__(DeviceCOO)
+        coo.ctx, coo.dtype, coo.h = ctx, np.dtype(dtype), h
+        return coo
+
     def __len__(self):
         n = C.c_int64()
         _lib.call("pa_coo_size", self.h, C.byref(n))
@@ -527,6 +542,7 @@ class DeviceMatrix:
         self.h = h
         self.ctx = ctx
         self.dtype = np.dtype(dtype)
+        self.csr_bi = None  # the parent's kind: None a SparseMatrixCSC, 0 / 1 a SparseMatrixCSR{Bi}
 
     @staticmethod
     def from_csc(ctx: PartContext, csc, rows_idx: DeviceIndex, cols_idx: DeviceIndex, nrows_lids, ncols_lids):
@@ -554,6 +570,7 @@ class DeviceMatrix:
                   nzval.ctypes.data_as(C.c_void_p), rows_idx.h, cols_idx.h, C.byref(h))
         M = DeviceMatrix(h, ctx, nzval.dtype)
         M.csc_nnz = len(nzval)
+        M.csr_bi = int(csr.Bi)
         return M
 
     @staticmethod
@@ -596,6 +613,7 @@ class DeviceMatrix:
                       V.ctypes.data_as(C.c_void_p), rows_idx.h, cols_idx.h, C.byref(nnz), *ptrs, C.byref(h))
         M = DeviceMatrix(h, ctx, V.dtype)
         M.csc_nnz = nnz.value
+        M.csr_bi = None if csr_bi is None else int(csr_bi)
         if not pattern:
             return M, None, None
         return M, colptr, rowval[:nnz.value].copy()
@@ -620,6 +638,7 @@ class DeviceMatrix:
                       rows_idx.h, cols_idx.h, C.byref(nnz), *ptrs, C.byref(h))
         M = DeviceMatrix(h, coo.ctx, coo.dtype)
         M.csc_nnz = nnz.value
+        M.csr_bi = None if csr_bi is None else int(csr_bi)
         if not pattern:
             return M, None, None
         return M, colptr, rowval[:nnz.value].copy()
@@ -686,6 +705,17 @@ class DeviceMatrix:
                   _lib.PA_IDS_GLOBAL if ids_global else _lib.PA_IDS_LOCAL, ib, 1 if absent_zero else 0,
                   1 if on_device else 0, n, ip, jp, op)
         return out
+
+    def findnz(self, rows_idx: DeviceIndex, cols_idx: DeviceIndex, all_rows=False, ids_global=True) -> DeviceCOO:
+        """pa_mat_findnz: the stored entries of the part as a new DeviceCOO
+        in the parent's nziterator order — of the owned rows, or with
+        all_rows of the stored ghost rows too; I, J 1-based lids, or gids
+        with ids_global (the indices then need their gid tables)."""
+        h = C.c_void_p()
+        _lib.call("pa_mat_findnz", self.h, rows_idx.h, cols_idx.h,
+                  _lib.PA_NZ_ALL_ROWS if all_rows else _lib.PA_NZ_OWNED_ROWS,
+                  _lib.PA_IDS_GLOBAL if ids_global else _lib.PA_IDS_LOCAL, C.byref(h))
+        return DeviceCOO._adopt(self.ctx, self.dtype, h)
 
     def entry_table(self):
         """pa_mat_entry_info: (entries, bytes) of the entry table the first

@@ -569,6 +569,45 @@ def to_lids_(ids: PData, a: PRange) -> PData:
     return map_parts(f, ids, a.partition)
 
 
+def to_gids_(ids: PData, a: PRange) -> PData:
+    """to_gids! (Interfaces.jl:1545-1547, 638-645): the Int64 lids of every
+    part become gids in place.  On HIP parts the translation runs through
+    the device's lid_to_gid (pa_index_to_gids); a lid outside 1..num_lids
+    raises and leaves the part's ids unchanged."""
+    backend = a.partition.backend
+    if hasattr(backend, "context"):
+        from .device import device_to_gids
+        lookup = lambda l, s: device_to_gids(backend.context(s.part), s, l)
+    else:
+        def lookup(l, s):
+            l = np.asarray(l, dtype=np.int64)
+            if len(l) and (l.min() < 1 or l.max() > s.num_lids):
+                raise IndexError(f"to_gids!: a local id is out of range on part {s.part} (BoundsError)")
+            return s.lid_to_gid[l - 1]
+
+    def f(l, s):
+        l[...] = lookup(l, s)
+        return l
+    return map_parts(f, ids, a.partition)
+
+
+def to_main(rows: PRange) -> PRange:
+    """_to_main(rows) (Interfaces.jl:2734-2748): the range over the same gids
+    in which MAIN holds lids 1..ngids and owns all of them, and every other
+    part holds the gids of its own oids, in oid order, as lids owned by MAIN
+    (a part without oids has zero lids).  Its exchanger sends MAIN's values
+    to those parts (exchange!) and adds theirs onto MAIN's (assemble!)."""
+    ngids = len(rows)
+
+    def mk(s: IndexSet):
+        if s.part == MAIN:
+            g = np.arange(1, ngids + 1, dtype=np.int64)
+        else:
+            g = s.lid_to_gid[s.oid_to_lid - 1].copy()
+        return IndexSet(s.part, g, np.full(len(g), MAIN, dtype=np.int32))
+    return prange_from_partition(ngids, map_parts(mk, rows.partition))
+
+
 def _cached_eq(kind, a: PRange, b: PRange, f):
     # the @check of mul!/copyto!/broadcasts (Interfaces.jl:1550-1554) is a
     # gather+bcast per call in the reference; the partitions are immutable

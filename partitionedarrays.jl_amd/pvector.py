@@ -16,12 +16,13 @@ import weakref
 import numpy as np
 
 from . import _lib
-from .backends import PData, exchange, get_part_ids, map_parts, unzip
-from .device import (DeviceArray, DeviceCOO, DeviceMatrix, DeviceMatrixExchanger, DeviceVector, Task, contexts,
-                     device_exchanger, device_index, device_index_gids)
+from .backends import MAIN, PData, exchange, get_part_ids, map_parts, unzip
+from .backends import gather as _gather_pdata
+from .device import (DeviceArray, DeviceCOO, DeviceIndex, DeviceMatrix, DeviceMatrixExchanger, DeviceVector, Task,
+                     contexts, device_exchanger, device_index, device_index_gids)
 from .helpers import Table, counts_to_ptrs, trace_setup
 from .prange import (Exchanger, PRange, _cached_eq, add_gids_, empty_exchanger, hids_are_equal, oids_are_equal,
-                     prange_linear)
+                     prange_linear, to_main)
 
 
 # ---------------------------------------------------------------------------
@@ -1086,17 +1087,20 @@ class PSparseMatrix:
                                    rows.partition.shape), rows, cols, ex)
 
     @staticmethod
-    def from_coo(I, J, V, rows: PRange, cols: PRange, ids="local", init=None):
+    def from_coo(I, J, V, rows: PRange, cols: PRange, ids="local", init=None, exchanger=None):
         """PSparseMatrix(init, I, J, V, rows, cols; ids) (Interfaces.jl:
-        2194-2215).  init None = sparse (2237-2244), on the device; I, J, V:
+        2194-2215; `exchanger`: the matrix exchanger the caller supplies, as
+        gather(A) passes an empty one, 2699-2702 — device compress only).  init None = sparse (2237-2244), on the device; I, J, V:
         PData of host arrays, or I a device COO (then J and V are None).
         init = csr_init(Bi) (sparsecsr): the same compress on the device into
         SparseMatrixCSR{Bi} parents (pa_mat_from_coo_csr).  Another callable
         init compresses each part's host triplets and uploads the result
         (pa_mat_from_csc / pa_mat_from_csr)."""
         if isinstance(init, csr_init):  # sparsecsr on the device
-            return PSparseMatrix._from_coo_device(I, J, V, rows, cols, ids, csr_bi=init.Bi)
+            return PSparseMatrix._from_coo_device(I, J, V, rows, cols, ids, csr_bi=init.Bi, exchanger=exchanger)
         if init is not None:
+            if exchanger is not None:
+                raise NotImplementedError("from_coo: a custom init builds its own matrix exchanger")
             if isinstance(I, COO):
                 raise NotImplementedError("from_coo: a custom init needs host triplets")
             if ids == "global":
@@ -1109,10 +1113,10 @@ class PSparseMatrix:
             if all(isinstance(m, CSC) for m in loc.parts):
                 return PSparseMatrix.from_csc(loc, rows, cols)
             raise TypeError("from_coo: init must return CSC or CSR local matrices")
-        return PSparseMatrix._from_coo_device(I, J, V, rows, cols, ids)
+        return PSparseMatrix._from_coo_device(I, J, V, rows, cols, ids, exchanger=exchanger)
 
     @staticmethod
-    def _from_coo_device(I, J, V, rows: PRange, cols: PRange, ids="local", csr_bi=None):
+    def _from_coo_device(I, J, V, rows: PRange, cols: PRange, ids="local", csr_bi=None, exchanger=None):
         # to_lids! (ids=:global) and sparse(I, J, V) (or sparsecsr) on the
         # device (pa_mat_from_coo[_csr]); the host keeps the pattern only, for
         # matrix_exchanger
@@ -1125,7 +1129,7 @@ class PSparseMatrix:
         mats, pats = [], []
         # the host needs the CSC pattern only for matrix_exchanger, i.e. when
         # rows have ghosts (stored ghost rows of FE assembly)
-        want_pattern = bool(rows.ghost)
+        want_pattern = bool(rows.ghost) and exchanger is None
         trace = trace_setup()
         t0 = trace()
         for c, i, j, v, r, s in zip(ctxs, I.parts, J.parts, V.parts, rows.partition.parts, cols.partition.parts):
@@ -1146,7 +1150,7 @@ class PSparseMatrix:
         t1 = trace("device sparse + SELL, all parts", t0)
         backend, pids, shape = rows.partition.backend, rows.partition.part_ids, rows.partition.shape
         ex = (matrix_exchanger(PData(backend, pids, pats, shape), rows, cols) if want_pattern
-              else empty_exchanger(rows.partition))
+              else exchanger if exchanger is not None else empty_exchanger(rows.partition))
         trace("matrix_exchanger", t1)
         return PSparseMatrix(PData(backend, pids, mats, shape), rows, cols, ex)
 
@@ -1445,3 +1449,224 @@ def _cg_device(x: PVector, A: PSparseMatrix, b: PVector, reltol, abstol, maxiter
     if history is not None:
         history.extend(float(v) for v in hist[:its.value])
     return x
+
+
+# ---------------------------------------------------------------------------
+# Gather to MAIN and direct solves (Interfaces.jl:2626-2757).  Not efficient,
+# just for convenience and debugging purposes, as the reference says of its
+# own: the whole system moves to MAIN and is factored there on the host.  The
+# device does the rest: reading the stored entries back (pa_mat_findnz),
+# moving them and the vectors to MAIN (the COO and vector assemble) and
+# scattering the solution (the vector exchange).
+
+def findnz(A: PSparseMatrix, rows="owned", ids="global") -> COO:
+    """findnz / nziterator of every part of A on the device (pa_mat_findnz):
+    a COO whose parts hold the stored entries in the parent's storage order —
+    rows="owned": of the rows the part owns (the filter of gather(A),
+    Interfaces.jl:2671-2687), rows="all": of the stored ghost rows too;
+    ids="global" (gids) or "local" (lids of A.rows / A.cols).  The COO
+    composes with assemble_, exchange_, PSparseMatrix.from_coo and to_host."""
+    if rows not in ("owned", "all"):
+        raise ValueError("findnz: rows must be 'owned' or 'all'")
+    if ids not in ("global", "local"):
+        raise ValueError("findnz: ids must be 'global' or 'local'")
+    glob = ids == "global"
+    parts = [M.findnz(r, c, all_rows=rows == "all", ids_global=glob)
+             for M, (r, c) in zip(A.values.parts, _mat_index(A, glob))]
+    p = A.values
+    return COO(PData(p.backend, p.part_ids, parts, p.shape))
+
+
+class _OwnedMap:
+    """An index set whose "owned" lids are the places `target` (1-based lids
+    of an n-vector) in order: pa_vec_copy between it and a range's own index
+    set moves the range's owned values to or from those places."""
+
+    def __init__(self, n, target):
+        self.oid_to_lid = np.asarray(target, dtype=np.int32)
+        rest = np.ones(n, dtype=bool)
+        rest[self.oid_to_lid - 1] = False
+        self.hid_to_lid = (np.flatnonzero(rest) + 1).astype(np.int32)
+        self.num_lids, self.num_oids, self.num_hids = int(n), len(self.oid_to_lid), len(self.hid_to_lid)
+
+
+def _main_maps(rows: PRange, rows_in_main: PRange):
+    """per part, the device index over rows_in_main's lids that places the
+    owned values of rows: by gid on MAIN, in oid order elsewhere
+    (Interfaces.jl:2709-2716); rows_in_main must be a to_main range of rows"""
+    if rows.partition.part_ids != rows_in_main.partition.part_ids or len(rows) != len(rows_in_main):
+        raise ValueError("gather / scatter!: the range in MAIN is not one of this range (parts or length differ)")
+    cache = rows_in_main.__dict__.setdefault("_main_maps", {})
+    hit = cache.get(id(rows.partition))
+    if hit is not None and hit[0] is rows.partition:
+        return hit[1]
+    maps = []
+    for c, s, m in zip(contexts(rows.partition), rows.partition.parts, rows_in_main.partition.parts):
+        own = s.lid_to_gid[s.oid_to_lid - 1]
+        if s.part == MAIN:
+            ok = m.num_lids == len(rows) and np.array_equal(m.lid_to_gid, np.arange(1, len(rows) + 1))
+            target = own
+        else:
+            ok = np.array_equal(m.lid_to_gid, own)
+            target = np.arange(1, len(own) + 1)
+        if not ok:
+            raise ValueError(f"gather / scatter!: the range in MAIN does not hold this range's ids on part {s.part}")
+        maps.append(DeviceIndex(c, _OwnedMap(m.num_lids, target)))
+    cache[id(rows.partition)] = (rows.partition, maps)
+    return maps
+
+
+def gather(x, rows_in_main: PRange = None, cols_in_main: PRange = None):
+    """gather(a) of a PData: the parts' values collected on MAIN
+    (backends.gather).  Not efficient, for convenience and debugging:
+
+    gather(b::PVector, rows_in_main = to_main(b.rows)) (Interfaces.jl:
+    2706-2719): b_in_main = PVector(zero(T), rows_in_main) takes b's owned
+    values — by gid on MAIN, in oid order on the other parts — and
+    assemble!(b_in_main) adds them onto MAIN's, all on the device.
+
+    gather(A::PSparseMatrix, rows_in_main, cols_in_main) (2664-2704):
+    findnz(A, "owned", "global"), assemble!(I, J, V, rows_in_main), the
+    triplets of the parts other than MAIN dropped, and PSparseMatrix(I, J, V,
+    rows_in_main, cols_in_main; ids=:global) with A's parent kind and an
+    empty exchanger: MAIN holds the whole matrix, the others an empty one."""
+    if isinstance(x, PData):
+        if rows_in_main is not None or cols_in_main is not None:
+            raise TypeError("gather(a::PData) takes no ranges")
+        return _gather_pdata(x)
+    if isinstance(x, PVector):
+        if cols_in_main is not None:
+            raise TypeError("gather(b, rows_in_main): a PVector has no cols")
+        rows_in_main = rows_in_main if rows_in_main is not None else to_main(x.rows)
+        maps = _main_maps(x.rows, rows_in_main)
+        b_in_main = PVector.full(0, rows_in_main, dtype=x.dtype)
+        for d, m, v, i in zip(b_in_main.values.parts, maps, x.values.parts, _idx(x)):
+            _lib.call("pa_vec_copy", d.h, m.h, v.h, i, 0)
+        return assemble_(b_in_main)
+    if not isinstance(x, PSparseMatrix):
+        raise TypeError("gather: a PData, a PVector or a PSparseMatrix")
+    rows_in_main = rows_in_main if rows_in_main is not None else to_main(x.rows)
+    cols_in_main = cols_in_main if cols_in_main is not None else to_main(x.cols)
+    _main_maps(x.rows, rows_in_main), _main_maps(x.cols, cols_in_main)  # the ranges are the matrix's
+    coo = assemble_(findnz(x, "owned", "global"), rows_in_main)
+    p = coo.values
+    none = np.zeros(0, np.int64)
+    kept = [c if part == MAIN else DeviceCOO(c.ctx, none, none, np.zeros(0, c.dtype))
+            for c, part in zip(p.parts, p.part_ids)]
+    bi = x.values.parts[0].csr_bi
+    return PSparseMatrix.from_coo(COO(PData(p.backend, p.part_ids, kept, p.shape)), None, None, rows_in_main,
+                                  cols_in_main, ids="global", init=None if bi is None else csr_init(bi),
+                                  exchanger=empty_exchanger(rows_in_main.partition))
+
+
+def scatter_(c: PVector, c_in_main: PVector) -> PVector:
+    """scatter!(c, c_in_main) (Interfaces.jl:2721-2732): exchange!(c_in_main)
+    sends MAIN's values to the parts, then c's owned values are taken from
+    it (by gid on MAIN, in oid order elsewhere); c's ghost values stay."""
+    if np.dtype(c.dtype) != np.dtype(c_in_main.dtype):
+        raise TypeError("scatter!: element types differ")
+    maps = _main_maps(c.rows, c_in_main.rows)
+    exchange_(c_in_main)
+    for d, i, v, m in zip(c.values.parts, _idx(c), c_in_main.values.parts, maps):
+        _lib.call("pa_vec_copy", d.h, i, v.h, m.h, 0)
+    return c
+
+
+class _DenseLU:
+    """the numpy.linalg stand-in for a sparse LU of a small matrix"""
+
+    def __init__(self, a):
+        self.a = a
+
+    def solve(self, b):
+        return np.linalg.solve(self.a, b)
+
+
+def _main_lu(csc: CSC):
+    """The factorisation of MAIN's gathered matrix, on the host: an object
+    with solve(b).  csc is the canonical local CSC (rows ascending in every
+    column, no duplicates).  scipy.sparse.linalg.splu when scipy is there;
+    without it a dense numpy.linalg solve up to 8192 unknowns."""
+    if csc.m != csc.n:
+        raise _lib.PAError(f"lu: the matrix is not square ({csc.m} x {csc.n})")
+    try:
+        from scipy.sparse import csc_matrix
+        from scipy.sparse.linalg import splu
+    except ImportError:
+        if csc.n > 8192:
+            raise _lib.PAError(f"lu: {csc.n} unknowns need scipy.sparse.linalg.splu, and scipy cannot be imported "
+                               "(the dense numpy.linalg fallback stops at 8192)")
+        a = np.zeros((csc.m, csc.n), dtype=csc.nzval.dtype)
+        a[csc.rowval - 1, np.repeat(np.arange(csc.n), np.diff(csc.colptr))] = csc.nzval
+        return _DenseLU(a)
+    return splu(csc_matrix((csc.nzval, csc.rowval - 1, csc.colptr - 1), shape=(csc.m, csc.n)))
+
+
+def _main_csc(a_in_main: PSparseMatrix, dtype=None):
+    """MAIN's gathered local matrix on the host as the canonical CSC (None
+    where this process does not hold MAIN): the findnz download, compressed"""
+    for part, M, (r, c), s, t in zip(a_in_main.values.part_ids, a_in_main.values.parts, _mat_index(a_in_main, False),
+                                     a_in_main.rows.partition.parts, a_in_main.cols.partition.parts):
+        if part == MAIN:
+            I, J, V = M.findnz(r, c, all_rows=True, ids_global=False).download()
+            return compresscoo(I, J, V.astype(dtype or V.dtype), s.num_lids, t.num_lids)
+    return None
+
+
+class PLU:
+    """PLU (Interfaces.jl:2641-2645): MAIN's factors and the ranges in MAIN.
+    Not efficient, for convenience and debugging."""
+
+    def __init__(self, lu_in_main, rows: PRange, cols: PRange, dtype, src_rows: PRange, src_cols: PRange):
+        self.lu_in_main, self.rows, self.cols, self.dtype = lu_in_main, rows, cols, np.dtype(dtype)
+        self._src = (src_rows, src_cols)
+
+
+def _factor(a_in_main, dtype):
+    csc = _main_csc(a_in_main, dtype)
+    return _main_lu(csc) if csc is not None else None
+
+
+def lu(A: PSparseMatrix, dtype=None) -> PLU:
+    """lu(A) (Interfaces.jl:2646-2650): gather(A), then the LU on MAIN's host
+    (_main_lu).  Not efficient, for convenience and debugging."""
+    a_in_main = gather(A)
+    dtype = np.dtype(dtype or A.dtype)
+    return PLU(_factor(a_in_main, dtype), a_in_main.rows, a_in_main.cols, dtype, A.rows, A.cols)
+
+
+def lu_(F: PLU, A: PSparseMatrix) -> PLU:
+    """lu!(F, A) (Interfaces.jl:2651-2655): A gathered again through F.rows
+    and F.cols — the ranges in MAIN and their exchangers are reused — and
+    factored anew."""
+    F.lu_in_main = _factor(gather(A, F.rows, F.cols), F.dtype)
+    F._src = (A.rows, A.cols)
+    return F
+
+
+def ldiv_(c: PVector, F: PLU, b: PVector) -> PVector:
+    """ldiv!(c, F, b) (Interfaces.jl:2656-2662): b gathered through F.rows,
+    solved on MAIN's host, and scattered into c's owned values."""
+    b_in_main = gather(b, F.rows)
+    c_in_main = PVector.full(0, F.cols, dtype=c.dtype)
+    _main_maps(c.rows, F.cols)
+    for part, vb, vc in zip(b_in_main.values.part_ids, b_in_main.values.parts, c_in_main.values.parts):
+        if part == MAIN:
+            x = F.lu_in_main.solve(vb.download().astype(F.dtype))
+            vc.upload(np.ascontiguousarray(x, dtype=c.dtype))
+    return scatter_(c, c_in_main)
+
+
+def zerox(A: PSparseMatrix, b: PVector) -> PVector:
+    """IterativeSolvers.zerox(A, b) (Interfaces.jl:2752-2757): zeros of the
+    solve's element type over A.cols."""
+    return PVector.full(0, A.cols, dtype=np.result_type(A.dtype, b.dtype))
+
+
+def solve(A: PSparseMatrix, b: PVector) -> PVector:
+    """A \\ b (Interfaces.jl:2626-2638).  Not efficient, just for convenience
+    and debugging purposes: A and b are gathered on MAIN (on the device),
+    MAIN's host factors and solves, and the solution is scattered over
+    A.cols.  The element type is numpy.result_type of the two."""
+    c = zerox(A, b)
+    return ldiv_(c, lu(A, dtype=c.dtype), b)
