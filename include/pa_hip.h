@@ -279,7 +279,10 @@ int pa_vec_copy(pa_vec* dst, const pa_index* idx_dst,
  *   mode 3: y[i] = y[i] - x[i]       (r .-= c)
  *   mode 4: y[i] = a*y[i]            (rmul!, Interfaces.jl:1675)
  * over all lids when all_lids != 0 (same partition: ghosts too), else over
- * the owned values through idx (which must describe both vectors).
+ * the owned values through idx, which must describe both vectors: the same
+ * lid layout, not merely equal owned ids (x is read at y's lids; vectors of
+ * equal owned ids in another lid order, or next to other ghosts, take
+ * pa_vec_eval, which has one index set per operand).
  * The scalar a is of the element type, or — mode | PA_BCAST_F64 — a
  * Float64 (double), or — mode | PA_BCAST_C128 — a ComplexF64 (complex
  * vectors only): then each element is evaluated in Float64 / ComplexF64

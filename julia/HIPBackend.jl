@@ -46,7 +46,7 @@ import Distances
 import PartitionedArrays: get_part_ids, map_parts, i_am_main, get_backend, get_part, gather!,
   gather_all!, scatter, async_exchange!, async_assemble!, num_parts, prun_debug, PVector,
   PSparseMatrix, PRange, SequentialData, AbstractPData, AbstractBackend, Table, Exchanger, MAIN,
-  num_lids, num_oids, num_hids, oids_are_equal, hids_are_equal
+  num_lids, num_oids, num_hids, oids_are_equal, hids_are_equal, lids_are_equal
 
 export HIPBackend, HIPData
 
@@ -969,9 +969,26 @@ _bcast_scalar(::Type{T}, a::Float64) where {T} = (Ref{Float64}(a), PA_BCAST_F64)
 _bcast_scalar(::Type{T}, a::ComplexF64) where {T<:Complex} = (Ref{ComplexF64}(a), PA_BCAST_C128)
 _bcast_scalar(::Type{T}, a) where {T} = (Ref{T}(T(a)), Cint(0))
 
+# the named pattern `mode` as a tree over y and x; the scalar keeps
+# _bcast_scalar's typing (anything but a widening Float64 / ComplexF64 is a T)
+function _axpby_tree(y::HIPVector{T}, x::HIPVector{T}, a, mode::Integer) where {T<:DeviceEltype}
+  s = (a isa Float64 || (a isa ComplexF64 && T <: Complex)) ? a : T(a)
+  mode == 0 && return _expr_node(+, x, _expr_node(*, s, y))
+  mode == 1 && return _expr_node(+, y, _expr_node(*, s, x))
+  mode == 2 && return _expr_node(-, y, _expr_node(*, s, x))
+  _expr_node(-, y, x)
+end
+
 function _axpby!(y::HIPVector{T}, x::Union{Nothing,HIPVector{T}}, a, mode::Integer) where {T<:DeviceEltype}
   all_lids = x === nothing || y.rows === x.rows
   x === nothing || all_lids || @assert oids_are_equal(y.rows, x.rows)
+  # pa_vec_axpby reads x through y's index set: only for one lid layout.  Equal
+  # owned ids in another lid order (or next to other ghosts) go through
+  # pa_vec_eval, which carries one index set per operand.
+  if x !== nothing && !all_lids && !lids_are_equal(y.rows, x.rows)
+    bc = _axpby_tree(y, x, a, mode)
+    return _expr_eval!(y, _expr_encode(T, bc), bc)
+  end
   s, kind = _bcast_scalar(T, a)
   yv, xv, iy = dev_vec(y), (x === nothing ? fill(C_NULL, num_parts(y.values)) : dev_vec(x)), dev_idx(y.rows)
   for i in eachindex(yv)

@@ -642,5 +642,4 @@ def hids_are_equal(a: PRange, b: PRange) -> bool:
 def lids_are_equal(a: PRange, b: PRange) -> bool:
     if a.partition is b.partition:
         return True
-    c = map_parts(lambda x, y: bool(np.array_equal(x.lid_to_gid, y.lid_to_gid)), a.partition, b.partition)
-    return bool(preduce(lambda u, v: u and v, c, True))
+    return _cached_eq("lids", a, b, lambda x, y: bool(np.array_equal(x.lid_to_gid, y.lid_to_gid)))

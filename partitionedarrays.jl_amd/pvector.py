@@ -21,8 +21,8 @@ from .backends import gather as _gather_pdata
 from .device import (DeviceArray, DeviceCOO, DeviceIndex, DeviceMatrix, DeviceMatrixExchanger, DeviceVector, Task,
                      contexts, device_exchanger, device_index, device_index_gids)
 from .helpers import Table, counts_to_ptrs, trace_setup
-from .prange import (Exchanger, PRange, _cached_eq, add_gids_, empty_exchanger, hids_are_equal, oids_are_equal,
-                     prange_linear, to_main)
+from .prange import (Exchanger, PRange, _cached_eq, add_gids_, empty_exchanger, hids_are_equal, lids_are_equal,
+                     oids_are_equal, prange_linear, to_main)
 
 
 # ---------------------------------------------------------------------------
@@ -478,12 +478,29 @@ def _scalar_kind(a, dtype):
     return a, 0
 
 
+def _bcast_expr(y: PVector, x: PVector, a, kind, mode):
+    """the named broadcast `mode` as an expression over y and x; the scalar
+    keeps pa_vec_axpby's typing (kind 0: converted to the element type)"""
+    if kind == 0:
+        a = np.dtype(y.dtype).type(a)
+    if mode == 0:
+        return x + a * y
+    if mode == 1:
+        return y + a * x
+    return y - a * x if mode == 2 else y - x
+
+
 def _bcast(y: PVector, x: PVector, a, mode):
     all_lids = 1 if (x is None or y.rows is x.rows) else 0
     if x is not None and not all_lids and not oids_are_equal(y.rows, x.rows):
         raise AssertionError("broadcast: owned ids differ")
-    iy = _idx(y)
     a, kind = _scalar_kind(a if a is not None else 0, y.dtype)
+    if x is not None and not all_lids and not lids_are_equal(y.rows, x.rows):
+        # pa_vec_axpby reads x through y's index set: only for one lid layout.
+        # Equal owned ids in another lid order (or next to other ghosts) go
+        # through the expression path, which carries one map per operand.
+        return assign_(y, _bcast_expr(y, x, a, kind, mode))
+    iy = _idx(y)
     mode |= kind
     buf, bp = _lib.scalar_buf(a, a.dtype if kind else y.dtype)
     xs = x.values.parts if x is not None else [None] * len(y.values.parts)

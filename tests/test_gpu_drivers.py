@@ -3,6 +3,8 @@ COO assembly with ghost rows, assemble! of the rhs, CG) against the oracle."""
 import numpy as np
 import pytest
 
+import blas1_ref
+
 pytestmark = pytest.mark.gpu
 
 
@@ -76,6 +78,12 @@ def test_fused_cg_kernels(be, pamd, O, fmt, shape, N, dtype):
             assert np.array_equal(x.to_host().local(p), x2.to_host().local(p))
             assert np.array_equal(r.to_host().local(p), r2.to_host().local(p))
         assert abs(nr - nr2) <= tol * nr2
+        # and against the independent reference: x + α u and r - α c over all
+        # lids (u's ghosts as the halo update left them, c as mul_dot_ left it)
+        hu, hc = u.to_host(), c.to_host()
+        for p in parts.part_ids:
+            assert blas1_ref.same_bits(x.to_host().local(p), blas1_ref.bcast("axpy", vals["x"][p], hu.local(p), alpha))
+            assert blas1_ref.same_bits(r.to_host().local(p), blas1_ref.bcast("axmy", vals["r"][p], hc.local(p), alpha))
     finally:
         pamd._lib.tune("spmv_format", prev)
 

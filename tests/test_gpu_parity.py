@@ -158,7 +158,7 @@ def test_exchange_assemble_bitexact(be, pamd, O, halo):
         assert np.array_equal(w.to_host().local(p), ow.values[p])
 
 
-@pytest.mark.parametrize("dtype", [np.float64, np.float32, np.complex128])
+@pytest.mark.parametrize("dtype", [np.float64, np.float32, np.complex128, np.complex64])
 def test_dot_norm_sum(be, pamd, O, dtype):
     shape, N = (2, 2, 1), (10, 9, 8)
     parts = be.get_part_ids(shape)

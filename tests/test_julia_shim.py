@@ -121,6 +121,17 @@ def test_every_helper_is_defined():
         assert re.search(sig, CODE), sig
 
 
+def test_axpby_routes_other_lid_layouts_to_the_expression_path():
+    """pa_vec_axpby reads x at y's lids: _axpby! hands vectors whose lid
+    layouts differ to pa_vec_eval before it reaches the ccall"""
+    start = CODE.index("function _axpby!(")
+    body = CODE[start:CODE.index("\nend\n", start)]
+    assert "!lids_are_equal(y.rows, x.rows)" in body and "_expr_eval!(y," in body
+    assert body.index("lids_are_equal") < body.index("ccall((:pa_vec_axpby")
+    imp = re.search(r"import PartitionedArrays:(.*?)\n\n", CODE, flags=re.S).group(1)
+    assert "lids_are_equal" in [n.strip() for n in imp.replace("\n", " ").split(",")]
+
+
 def test_reference_names_exist():
     ref = "/root/reference/src"
     if not os.path.isdir(ref):
