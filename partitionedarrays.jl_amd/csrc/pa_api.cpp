@@ -2272,86 +2272,122 @@ int pa_vec_axpby(pa_vec* y, const pa_vec* x, const pa_index* idx, const void* a,
   return 0;
 }
 
-// the argument checks pa_vec_scatter and pa_vec_gather share (no device
-// needed; the scalar arguments first, so that they are reported whatever the
-// handles are)
-static int vec_ids_check(const char* who, const pa_vec* v, const pa_index* idx, int ids_kind, int index_bytes,
-                         int64_t n, const void* I, const void* vals) {
-  const std::string w = std::string(who) + ": ";
+// ---------------------------------------------------------------------------
+// Access by id (pa_vec_scatter / pa_vec_gather, pa_mat_scatter /
+// pa_mat_gather, pa_mat_findnz): the checks, the staging of host arrays and
+// the messages the calls share.  `w` is the call's "pa_…: " prefix.
+
+// the scalar arguments (no device needed; first, so that they are reported
+// whatever the handles are)
+static int ids_scalar_check(const std::string& w, int ids_kind, int index_bytes, int64_t n) {
   CHECK_ARG(ids_kind == PA_IDS_LOCAL || ids_kind == PA_IDS_GLOBAL, w + "ids_kind must be PA_IDS_LOCAL or PA_IDS_GLOBAL");
   CHECK_ARG(index_bytes == 4 || index_bytes == 8, w + "index_bytes must be 4 or 8");
   CHECK_ARG(ids_kind != PA_IDS_GLOBAL || index_bytes == 8, w + "ids=:global needs Int64 ids (index_bytes 8)");
   CHECK_ARG(n >= 0, w + "negative length");
-  CHECK_ARG(v && idx && (n == 0 || (I && vals)), w + "null argument");
+  return 0;
+}
+
+// the handles of a vector call; arrays: the call's array arguments are there
+static int vec_handle_check(const std::string& w, const pa_vec* v, const pa_index* idx, bool arrays, int ids_kind) {
+  CHECK_ARG(v && idx && arrays, w + "null argument");
   CHECK_ARG(v->ctx == idx->ctx, w + "the vector and the index set belong to different parts");
   CHECK_ARG(v->n == idx->nlids, w + "the index set does not have the vector's local ids");
   CHECK_ARG(ids_kind != PA_IDS_GLOBAL || idx->has_gids, w + "call pa_index_set_gids first");
   return 0;
 }
 
-// a device array of `bytes` bytes for a call's input: the caller's own
-// (on_device) or a copy of the host array in `own`, enqueued on st
-static int vec_stage(int on_device, const void* p, size_t bytes, DevBuf<void>& own, hipStream_t st, void** dev) {
-  *dev = const_cast<void*>(p);
-  if (on_device || bytes == 0) return 0;
-  HIPC(own.alloc(bytes));
-  HIPC(hipMemcpyAsync(own, p, bytes, hipMemcpyHostToDevice, st));
-  *dev = own.p;
+// the handles of a matrix call, in vec_handle_check's words and order
+static int mat_handle_check(const std::string& w, const pa_mat* A, const pa_index* rows, const pa_index* cols,
+                            bool arrays, int ids_kind) {
+  CHECK_ARG(A && rows && cols && arrays, w + "null argument");
+  CHECK_ARG(A->ctx == rows->ctx && A->ctx == cols->ctx, w + "the matrix and the index sets belong to different parts");
+  CHECK_ARG(A->nz_map, w + "matrix was not built from a CSC pattern");
+  CHECK_ARG(rows->nlids == A->nrows_lids && rows->noids == A->main.nrows && cols->nlids == A->ncols_lids,
+            w + "the index sets do not have the matrix's local ids");
+  CHECK_ARG(ids_kind != PA_IDS_GLOBAL || (rows->has_gids && cols->has_gids), w + "call pa_index_set_gids first");
   return 0;
+}
+
+// a call's array on the device: the caller's own (on_device), or a buffer
+// the call owns — a copy of the host input enqueued on st, or room for an
+// output that copy_back returns to the host
+struct Staged {
+  DevBuf<void> own;
+  void* dev = nullptr;
+  size_t bytes = 0;
+  int in(int on_device, const void* p, size_t nbytes, hipStream_t st) {
+    if (out(on_device, const_cast<void*>(p), nbytes)) return -1;
+    if (own.p) HIPC(hipMemcpyAsync(own, p, bytes, hipMemcpyHostToDevice, st));
+    return 0;
+  }
+  int out(int on_device, void* p, size_t nbytes) {
+    dev = p, bytes = nbytes;
+    if (on_device || bytes == 0) return 0;
+    HIPC(own.alloc(bytes));
+    dev = own.p;
+    return 0;
+  }
+  // an owned buffer's bytes into the host array, complete on return
+  int copy_back(void* host, hipStream_t st) {
+    if (!own.p) return 0;
+    HIPC(hipMemcpyAsync(host, own, bytes, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    return 0;
+  }
+};
+
+// what a device pass over ids returned, as the call's error: < 0 a HIP
+// failure, 1 an id without a lid (key_who: whose KeyError a global id is),
+// 2 an (i, j) the matrix does not store
+static int ids_rc_check(const std::string& w, int rc, bool global, const std::string& key_who) {
+  CHECK_ARG(rc >= 0, w + "device pass failed");
+  if (rc == 1 && global) PA_FAIL(key_who + "a global id is not a local id of the part (KeyError)");
+  if (rc == 1) PA_FAIL(w + "a local id is out of range (BoundsError)");
+  if (rc == 2) PA_FAIL(w + "an entry (i, j) is not stored: the pattern on the device is fixed, no entry is inserted");
+  return 0;
+}
+
+// the ordered scatter of n items into nl values sorts 64-bit keys and payloads
+static inline bool scatter_wide(int64_t nl, int64_t n) {
+  return knobs().scatter_wide || (uint64_t)nl > (1ull << 32) || (uint64_t)n > (1ull << 32);
 }
 
 int pa_vec_scatter(pa_vec* v, pa_index* idx, int ids_kind, int index_bytes, int op, int zero_first, int on_device,
                    int64_t n, void* I, const void* V) {
-  CHECK_ARG(op == PA_SCATTER_ADD || op == PA_SCATTER_SET, "pa_vec_scatter: op must be PA_SCATTER_ADD or PA_SCATTER_SET");
-  if (vec_ids_check("pa_vec_scatter", v, idx, ids_kind, index_bytes, n, I, V)) return -1;
+  const std::string w = "pa_vec_scatter: ";
+  CHECK_ARG(op == PA_SCATTER_ADD || op == PA_SCATTER_SET, w + "op must be PA_SCATTER_ADD or PA_SCATTER_SET");
+  if (ids_scalar_check(w, ids_kind, index_bytes, n) || vec_handle_check(w, v, idx, n == 0 || (I && V), ids_kind))
+    return -1;
   pa_ctx* c = v->ctx;
   TuneScope ts(c);
   HIPC(hipSetDevice(c->device));
   const bool global = ids_kind == PA_IDS_GLOBAL;
-  const size_t ibytes = (size_t)n * index_bytes;
-  DevBuf<void> bI, bV;
-  void *dI = nullptr, *dV = nullptr;
-  if (vec_stage(on_device, I, ibytes, bI, c->s_main, &dI) ||
-      vec_stage(on_device, V, (size_t)n * dtype_size(v->dtype), bV, c->s_main, &dV))
+  Staged sI, sV;
+  if (sI.in(on_device, I, (size_t)n * index_bytes, c->s_main) ||
+      sV.in(on_device, V, (size_t)n * dtype_size(v->dtype), c->s_main))
     return -1;
-  const bool wide = knobs().scatter_wide || (uint64_t)v->n > (1ull << 32) || (uint64_t)n > (1ull << 32);
-  const int rc = vec_scatter(v->dtype, v->n, v->d, global, index_bytes, op == PA_SCATTER_SET, zero_first != 0, wide, n,
-                             dI, dV, idx->d_sgid, idx->d_slid, c->s_main);
-  CHECK_ARG(rc >= 0, "pa_vec_scatter: device pass failed");
-  if (rc && global) PA_FAIL("to_lids!: a global id is not a local id of the part (KeyError)");
-  if (rc) PA_FAIL("pa_vec_scatter: a local id is out of range (BoundsError)");
-  if (global && !on_device && n > 0) {  // the caller's I holds the lids now
-    HIPC(hipMemcpyAsync(I, dI, ibytes, hipMemcpyDeviceToHost, c->s_main));
-    HIPC(hipStreamSynchronize(c->s_main));
-  }
-  return 0;
+  const int rc = vec_scatter(v->dtype, v->n, v->d, global, index_bytes, op == PA_SCATTER_SET, zero_first != 0,
+                             scatter_wide(v->n, n), n, sI.dev, sV.dev, idx->d_sgid, idx->d_slid, c->s_main);
+  if (ids_rc_check(w, rc, global, "to_lids!: ")) return -1;
+  return global ? sI.copy_back(I, c->s_main) : 0;  // the caller's I holds the lids now
 }
 
 int pa_vec_gather(const pa_vec* v, pa_index* idx, int ids_kind, int index_bytes, int absent_zero, int on_device,
                   int64_t n, const void* I, void* out) {
-  if (vec_ids_check("pa_vec_gather", v, idx, ids_kind, index_bytes, n, I, out)) return -1;
+  const std::string w = "pa_vec_gather: ";
+  if (ids_scalar_check(w, ids_kind, index_bytes, n) || vec_handle_check(w, v, idx, n == 0 || (I && out), ids_kind))
+    return -1;
   pa_ctx* c = v->ctx;
   HIPC(hipSetDevice(c->device));
   const bool global = ids_kind == PA_IDS_GLOBAL;
-  const size_t obytes = (size_t)n * dtype_size(v->dtype);
-  DevBuf<void> bI, bO;
-  void *dI = nullptr, *dO = out;
-  if (vec_stage(on_device, I, (size_t)n * index_bytes, bI, c->s_main, &dI)) return -1;
-  if (!on_device && n > 0) {
-    HIPC(bO.alloc(obytes));
-    dO = bO.p;
-  }
+  Staged sI, sO;
+  if (sI.in(on_device, I, (size_t)n * index_bytes, c->s_main) || sO.out(on_device, out, (size_t)n * dtype_size(v->dtype)))
+    return -1;
   // (a local id out of range is an error whatever absent_zero says)
-  const int rc = vec_gather(v->dtype, v->n, v->d, global, index_bytes, global && absent_zero != 0, n, dI, dO,
+  const int rc = vec_gather(v->dtype, v->n, v->d, global, index_bytes, global && absent_zero != 0, n, sI.dev, sO.dev,
                             idx->d_sgid, idx->d_slid, c->s_main);
-  CHECK_ARG(rc >= 0, "pa_vec_gather: device pass failed");
-  if (rc && global) PA_FAIL("pa_vec_gather: a global id is not a local id of the part (KeyError)");
-  if (rc) PA_FAIL("pa_vec_gather: a local id is out of range (BoundsError)");
-  if (!on_device && n > 0) {
-    HIPC(hipMemcpyAsync(out, dO, obytes, hipMemcpyDeviceToHost, c->s_main));
-    HIPC(hipStreamSynchronize(c->s_main));
-  }
-  return 0;
+  if (ids_rc_check(w, rc, global, w)) return -1;
+  return sO.copy_back(out, c->s_main);
 }
 
 // ---------------------------------------------------------------------------
@@ -3179,93 +3215,67 @@ int pa_mat_get_values(const pa_mat* A, void* nzval) {
 // built by the first call), and the vector scatter / gather runs over
 // main.val with them as local ids.
 
-// the argument checks the two calls share, in vec_ids_check's words and order
-static int mat_ids_check(const char* who, const pa_mat* A, const pa_index* rows, const pa_index* cols, int ids_kind,
-                         int index_bytes, int64_t n, const void* I, const void* J, const void* vals) {
-  const std::string w = std::string(who) + ": ";
-  CHECK_ARG(ids_kind == PA_IDS_LOCAL || ids_kind == PA_IDS_GLOBAL, w + "ids_kind must be PA_IDS_LOCAL or PA_IDS_GLOBAL");
-  CHECK_ARG(index_bytes == 4 || index_bytes == 8, w + "index_bytes must be 4 or 8");
-  CHECK_ARG(ids_kind != PA_IDS_GLOBAL || index_bytes == 8, w + "ids=:global needs Int64 ids (index_bytes 8)");
-  CHECK_ARG(n >= 0, w + "negative length");
-  CHECK_ARG(A && rows && cols && (n == 0 || (I && J && vals)), w + "null argument");
-  CHECK_ARG(A->ctx == rows->ctx && A->ctx == cols->ctx, w + "the matrix and the index sets belong to different parts");
-  CHECK_ARG(A->nz_map, w + "matrix was not built from a CSC pattern");
-  CHECK_ARG(rows->nlids == A->nrows_lids && rows->noids == A->main.nrows && cols->nlids == A->ncols_lids,
-            w + "the index sets do not have the matrix's local ids");
-  CHECK_ARG(ids_kind != PA_IDS_GLOBAL || (rows->has_gids && cols->has_gids), w + "call pa_index_set_gids first");
-  return 0;
-}
-
 // the value indices (1-based, 0: none) of the n entries of a call, in vidx
-static int mat_value_ids(const char* who, const pa_mat* cA, const pa_index* rows, const pa_index* cols, bool global,
-                         int index_bytes, bool absent_zero, bool stored, int64_t n, const void* dI, const void* dJ,
-                         DevBuf<int64_t>& vidx) {
-  const std::string w = std::string(who) + ": ";
+static int mat_value_ids(const std::string& w, const pa_mat* cA, const pa_index* rows, const pa_index* cols,
+                         bool global, int index_bytes, bool absent_zero, bool stored, int64_t n, const void* dI,
+                         const void* dJ, DevBuf<int64_t>& vidx) {
   pa_mat* A = const_cast<pa_mat*>(cA);  // the table is built on first use, as the nz map is loaded
   hipStream_t st = A->ctx->s_main;
   CHECK_ARG(A->has_entries || mat_entry_table(A, rows, st) == 0, w + "building the entry table failed");
   HIPC(vidx.alloc(n));
-  const int rc = mat_entry_ids(A, rows, cols, global, index_bytes, absent_zero, stored, n, dI, dJ, vidx, st);
-  CHECK_ARG(rc >= 0, w + "device pass failed");
-  if (rc == 1 && global) PA_FAIL(w + "a global id is not a local id of the part (KeyError)");
-  if (rc == 1) PA_FAIL(w + "a local id is out of range (BoundsError)");
-  if (rc == 2) PA_FAIL(w + "an entry (i, j) is not stored: the pattern on the device is fixed, no entry is inserted");
-  return 0;
+  return ids_rc_check(w, mat_entry_ids(A, rows, cols, global, index_bytes, absent_zero, stored, n, dI, dJ, vidx, st),
+                      global, w);
 }
 
 int pa_mat_scatter(pa_mat* A, pa_index* rows, pa_index* cols, int ids_kind, int index_bytes, int op, int on_device,
                    int64_t n, const void* I, const void* J, const void* V) {
-  CHECK_ARG(op == PA_SCATTER_ADD || op == PA_SCATTER_SET, "pa_mat_scatter: op must be PA_SCATTER_ADD or PA_SCATTER_SET");
-  if (mat_ids_check("pa_mat_scatter", A, rows, cols, ids_kind, index_bytes, n, I, J, V)) return -1;
+  const std::string w = "pa_mat_scatter: ";
+  CHECK_ARG(op == PA_SCATTER_ADD || op == PA_SCATTER_SET, w + "op must be PA_SCATTER_ADD or PA_SCATTER_SET");
+  if (ids_scalar_check(w, ids_kind, index_bytes, n) ||
+      mat_handle_check(w, A, rows, cols, n == 0 || (I && J && V), ids_kind))
+    return -1;
   if (n == 0) return 0;
   pa_ctx* c = A->ctx;
   TuneScope ts(c);
   HIPC(hipSetDevice(c->device));
   const bool global = ids_kind == PA_IDS_GLOBAL;
   const size_t ibytes = (size_t)n * index_bytes;
-  DevBuf<void> bI, bJ, bV;
+  Staged sI, sJ, sV;
   DevBuf<int64_t> vidx;
-  void *dI = nullptr, *dJ = nullptr, *dV = nullptr;
-  if (vec_stage(on_device, I, ibytes, bI, c->s_main, &dI) || vec_stage(on_device, J, ibytes, bJ, c->s_main, &dJ) ||
-      vec_stage(on_device, V, (size_t)n * dtype_size(A->dtype), bV, c->s_main, &dV))
+  if (sI.in(on_device, I, ibytes, c->s_main) || sJ.in(on_device, J, ibytes, c->s_main) ||
+      sV.in(on_device, V, (size_t)n * dtype_size(A->dtype), c->s_main))
     return -1;
-  if (mat_value_ids("pa_mat_scatter", A, rows, cols, global, index_bytes, false, true, n, dI, dJ, vidx)) return -1;
+  if (mat_value_ids(w, A, rows, cols, global, index_bytes, false, true, n, sI.dev, sJ.dev, vidx)) return -1;
   const int64_t nv = nvals(A);
-  const bool wide = knobs().scatter_wide || (uint64_t)nv > (1ull << 32) || (uint64_t)n > (1ull << 32);
-  const int rc = vec_scatter(A->dtype, nv, A->main.val, false, 8, op == PA_SCATTER_SET, false, wide, n, vidx.p, dV,
-                             nullptr, nullptr, c->s_main);
-  CHECK_ARG(rc == 0, "pa_mat_scatter: device pass failed");
+  const int rc = vec_scatter(A->dtype, nv, A->main.val, false, 8, op == PA_SCATTER_SET, false, scatter_wide(nv, n), n,
+                             vidx.p, sV.dev, nullptr, nullptr, c->s_main);
+  CHECK_ARG(rc == 0, w + "device pass failed");
   return refresh_side(A, c->s_main);
 }
 
 int pa_mat_gather(const pa_mat* A, pa_index* rows, pa_index* cols, int ids_kind, int index_bytes, int absent_zero,
                   int on_device, int64_t n, const void* I, const void* J, void* out) {
-  if (mat_ids_check("pa_mat_gather", A, rows, cols, ids_kind, index_bytes, n, I, J, out)) return -1;
+  const std::string w = "pa_mat_gather: ";
+  if (ids_scalar_check(w, ids_kind, index_bytes, n) ||
+      mat_handle_check(w, A, rows, cols, n == 0 || (I && J && out), ids_kind))
+    return -1;
   if (n == 0) return 0;
   pa_ctx* c = A->ctx;
   HIPC(hipSetDevice(c->device));
   const bool global = ids_kind == PA_IDS_GLOBAL;
-  const size_t ibytes = (size_t)n * index_bytes, obytes = (size_t)n * dtype_size(A->dtype);
-  DevBuf<void> bI, bJ, bO;
+  const size_t ibytes = (size_t)n * index_bytes;
+  Staged sI, sJ, sO;
   DevBuf<int64_t> vidx;
-  void *dI = nullptr, *dJ = nullptr, *dO = out;
-  if (vec_stage(on_device, I, ibytes, bI, c->s_main, &dI) || vec_stage(on_device, J, ibytes, bJ, c->s_main, &dJ))
+  if (sI.in(on_device, I, ibytes, c->s_main) || sJ.in(on_device, J, ibytes, c->s_main) ||
+      sO.out(on_device, out, (size_t)n * dtype_size(A->dtype)))
     return -1;
-  if (!on_device) {
-    HIPC(bO.alloc(obytes));
-    dO = bO.p;
-  }
-  if (mat_value_ids("pa_mat_gather", A, rows, cols, global, index_bytes, global && absent_zero != 0, false, n, dI, dJ,
-                    vidx))
+  if (mat_value_ids(w, A, rows, cols, global, index_bytes, global && absent_zero != 0, false, n, sI.dev, sJ.dev, vidx))
     return -1;
   // value index 0 (not stored, or an absent id that may read zero): zero(T)
-  const int rc = vec_gather(A->dtype, nvals(A), A->main.val, false, 8, true, n, vidx.p, dO, nullptr, nullptr, c->s_main);
-  CHECK_ARG(rc == 0, "pa_mat_gather: device pass failed");
-  if (!on_device) {
-    HIPC(hipMemcpyAsync(out, dO, obytes, hipMemcpyDeviceToHost, c->s_main));
-    HIPC(hipStreamSynchronize(c->s_main));
-  }
-  return 0;
+  const int rc = vec_gather(A->dtype, nvals(A), A->main.val, false, 8, true, n, vidx.p, sO.dev, nullptr, nullptr,
+                            c->s_main);
+  CHECK_ARG(rc == 0, w + "device pass failed");
+  return sO.copy_back(out, c->s_main);
 }
 
 // findnz(A) / nziterator(A) of one part as a new device COO (pa_coo.hip,
@@ -3274,13 +3284,8 @@ int pa_mat_findnz(pa_mat* A, pa_index* rows, pa_index* cols, int which_rows, int
   const std::string w = "pa_mat_findnz: ";
   CHECK_ARG(which_rows == PA_NZ_OWNED_ROWS || which_rows == PA_NZ_ALL_ROWS,
             w + "which_rows must be PA_NZ_OWNED_ROWS or PA_NZ_ALL_ROWS");
-  CHECK_ARG(ids_kind == PA_IDS_LOCAL || ids_kind == PA_IDS_GLOBAL, w + "ids_kind must be PA_IDS_LOCAL or PA_IDS_GLOBAL");
-  CHECK_ARG(A && rows && cols && out, w + "null argument");
-  CHECK_ARG(A->ctx == rows->ctx && A->ctx == cols->ctx, w + "the matrix and the index sets belong to different parts");
-  CHECK_ARG(A->nz_map, w + "matrix was not built from a CSC pattern");
-  CHECK_ARG(rows->nlids == A->nrows_lids && rows->noids == A->main.nrows && cols->nlids == A->ncols_lids,
-            w + "the index sets do not have the matrix's local ids");
-  CHECK_ARG(ids_kind != PA_IDS_GLOBAL || (rows->has_gids && cols->has_gids), w + "call pa_index_set_gids first");
+  // (no id arrays come in: of the scalar arguments only ids_kind can fail)
+  if (ids_scalar_check(w, ids_kind, 8, 0) || mat_handle_check(w, A, rows, cols, out != nullptr, ids_kind)) return -1;
   pa_ctx* c = A->ctx;
   HIPC(hipSetDevice(c->device));
   auto C = std::make_unique<pa_coo>();

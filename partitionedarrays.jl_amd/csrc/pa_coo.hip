@@ -250,6 +250,20 @@ hipError_t exclusive_sum(const int64_t* in, int64_t* out, int64_t n, hipStream_t
   return e;
 }
 
+// rank = exclusive scan of the 0/1 flags; *count = the flagged items (the
+// last rank + the last flag, read back)
+hipError_t scan_count(const int64_t* flag, int64_t* rank, int64_t n, hipStream_t st, int64_t* count) {
+  int64_t last[2] = {0, 0};
+  *count = 0;
+  if (n <= 0) return hipSuccess;
+  hipError_t e = exclusive_sum(flag, rank, n, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(&last[0], rank + n - 1, 8, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(&last[1], flag + n - 1, 8, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  *count = last[0] + last[1];
+  return e;
+}
+
 template <typename T>
 void seg_sum_t(int64_t nu, int64_t n, const int64_t* start, const uint64_t* key, const int64_t* idx,
                const void* V, int64_t m, int64_t ncols, int csr, int32_t* crow, int32_t* ccol, void* cval,
@@ -333,7 +347,7 @@ int coo_row_order(int64_t nu, const int32_t* crow, const int32_t* ccol, const in
                   DevBuf<int64_t>& rowptr, DevBuf<int64_t>& gflag, DevBuf<int64_t>& grank, DevBuf<int32_t>& slen,
                   DevBuf<int32_t>& sghost, int64_t* nnz_out, int64_t* ngh_out, hipStream_t st, hipError_t* err) {
   const int64_t ns = (nrows + H - 1) / H;
-  int64_t nnz = 0, ngh = 0, last = 0, lastf = 0;
+  int64_t nnz = 0, ngh = 0;
   *nnz_out = *ngh_out = 0;
   *err = hipSuccess;
   const int64_t nb = nu > 0 ? nu : 1;
@@ -347,10 +361,7 @@ int coo_row_order(int64_t nu, const int32_t* crow, const int32_t* ccol, const in
   if (nu > 0) {
     hipLaunchKernelGGL(k_own_keys, grid1(nu), dim3(256), 0, st, nu, crow, ccol, rl2o, cl2o, noids_c, ncols, key2.p,
                        idx2.p, gflag.p);
-    PA_HIP_OR(*err = exclusive_sum(gflag, grank, nu, st), -1);
-    PA_HIP_OR(*err = copy_sync(&last, grank.p + nu - 1, 8, hipMemcpyDeviceToHost, st), -1);
-    PA_HIP_OR(*err = copy_sync(&lastf, gflag.p + nu - 1, 8, hipMemcpyDeviceToHost, st), -1);
-    ngh = last + lastf;
+    PA_HIP_OR(*err = scan_count(gflag, grank, nu, st, &ngh), -1);
     nnz = nu - ngh;
     // ghost rows carry key2 = ~0: sort all bits of the owned range + 1
     const uint64_t maxk = (uint64_t)(nrows > 0 ? nrows : 1) * (uint64_t)ncols;
@@ -540,14 +551,11 @@ int gids_first_touch(int64_t n, const int64_t* gids, const uint64_t* sgid, const
   if (n <= 0) return 0;
   DevBuf<int64_t> flag, pos, val, head, rank, val2;
   DevBuf<uint64_t> key, key2;
-  int64_t m = 0, lastf = 0, u = 0, maxg = 0;
+  int64_t m = 0, u = 0, maxg = 0;
   PA_HIP_OR(flag.alloc(n), -1);
   PA_HIP_OR(pos.alloc(n), -1);
   hipLaunchKernelGGL(k_absent, grid1(n), dim3(256), 0, st, n, gids, sgid, slid, nl, flag.p);
-  PA_HIP_OR(exclusive_sum(flag, pos, n, st), -1);
-  PA_HIP_OR(copy_sync(&m, pos.p + n - 1, 8, hipMemcpyDeviceToHost, st), -1);
-  PA_HIP_OR(copy_sync(&lastf, flag.p + n - 1, 8, hipMemcpyDeviceToHost, st), -1);
-  m += lastf;
+  PA_HIP_OR(scan_count(flag, pos, n, st, &m), -1);
   if (m == 0) return 0;
   PA_HIP_OR(key.alloc(m), -1);
   PA_HIP_OR(val.alloc(m), -1);
@@ -1004,7 +1012,7 @@ struct EntrySrc {
   const int32_t* long_row;
   const int64_t* long_ptr;
   const int32_t* long_col;
-  // pa_mat_findnz (zero for the entry table): column-major keys
+  // pa_mat_findnz (both switches 0 for the entry table): column-major keys
   // col_lid * nrl + row_lid, and the stored ghost rows left out
   int64_t nrl;
   int colmajor, owned_only;
@@ -1096,41 +1104,53 @@ __global__ void k_entry_ids(int64_t n, const IT* __restrict__ I, const IT* __res
   }
 }
 
-int mat_entry_table(pa_mat* A, const pa_index* rows, hipStream_t st) {
+// the stored entries of A as (key, value index) pairs sorted by key, into
+// ekey / eidx (*ne_out of them; none: both left empty).  colmajor: the key
+// is col_lid * nrows_lids + row_lid, else row_lid * ncols_lids + col_lid;
+// owned_only leaves the stored ghost rows out.  Emit over the value indices,
+// scan, compact, sort.
+static int entry_pairs(const pa_mat* A, const pa_index* rows, bool colmajor, bool owned_only, DevBuf<uint64_t>& ekey,
+                       DevBuf<int64_t>& eidx, int64_t* ne_out, hipStream_t st) {
   const int64_t nv = A->main.slots + A->n_gnz + A->n_lnz;
-  A->d_ekey.reset();
-  A->d_eidx.reset();
-  A->n_entries = 0;
-  if (nv > 0) {
-    DevBuf<uint64_t> key;
-    DevBuf<int64_t> flag, rank;
-    int64_t last[2] = {0, 0};
-    PA_HIP_OR(key.alloc(nv), -1);
-    PA_HIP_OR(flag.alloc(nv), -1);
-    PA_HIP_OR(rank.alloc(nv), -1);
-    const EntrySrc a = {A->main.slots, A->n_gnz, A->n_lnz, A->main.nrows, A->main.nslices, A->ncols_lids, A->n_long,
-                        A->H, A->R, A->main.off, A->main.col, A->d_kind, rows->own_contig ? nullptr : rows->d_oid_to_lid.p,
-                        A->d_ghost_rc, A->d_long_row, A->d_long_ptr, A->d_long_col, 0, 0, 0};
-    hipLaunchKernelGGL(k_entry_emit, grid1(nv), dim3(256), 0, st, a, key.p, flag.p);
-    PA_HIP_OR(hipGetLastError(), -1);
-    PA_HIP_OR(exclusive_sum(flag, rank, nv, st), -1);
-    PA_HIP_OR(hipMemcpyAsync(&last[0], rank.p + nv - 1, 8, hipMemcpyDeviceToHost, st), -1);
-    PA_HIP_OR(hipMemcpyAsync(&last[1], flag.p + nv - 1, 8, hipMemcpyDeviceToHost, st), -1);
-    PA_HIP_OR(hipStreamSynchronize(st), -1);
-    const int64_t ne = last[0] + last[1];
-    if (ne > 0) {
-      PA_HIP_OR(A->d_ekey.alloc(ne), -1);
-      PA_HIP_OR(A->d_eidx.alloc(ne), -1);
-      hipLaunchKernelGGL(k_entry_compact, grid1(nv), dim3(256), 0, st, nv, key.p, flag.p, rank.p, A->d_ekey.p,
-                         A->d_eidx.p);
-      PA_HIP_OR(hipGetLastError(), -1);
-      PA_HIP_OR(hipStreamSynchronize(st), -1);
-      key.reset(), flag.reset(), rank.reset();  // before the sort takes its buffers
-      const uint64_t maxk = (uint64_t)(A->nrows_lids > 0 ? A->nrows_lids : 1) * (uint64_t)A->ncols_lids;
-      PA_HIP_OR(sort_pairs(A->d_ekey, A->d_eidx, ne, bits_for(maxk), st), -1);
-    }
-    A->n_entries = ne;
-  }
+  int64_t ne = 0;
+  ekey.reset(), eidx.reset();
+  *ne_out = 0;
+  if (nv <= 0) return 0;
+  DevBuf<uint64_t> key;
+  DevBuf<int64_t> flag, rank;
+  PA_HIP_OR(key.alloc(nv), -1);
+  PA_HIP_OR(flag.alloc(nv), -1);
+  PA_HIP_OR(rank.alloc(nv), -1);
+  EntrySrc a;
+  a.slots = A->main.slots, a.n_gnz = A->n_gnz, a.n_lnz = A->n_lnz;
+  a.nrows = A->main.nrows, a.nslices = A->main.nslices, a.ncols = A->ncols_lids, a.n_long = A->n_long;
+  a.H = A->H, a.R = A->R;
+  a.off = A->main.off, a.col = A->main.col, a.kind = A->d_kind;
+  a.oid_to_lid = rows->own_contig ? nullptr : rows->d_oid_to_lid.p;
+  a.grc = A->d_ghost_rc;
+  a.long_row = A->d_long_row, a.long_ptr = A->d_long_ptr, a.long_col = A->d_long_col;
+  a.nrl = A->nrows_lids, a.colmajor = colmajor ? 1 : 0, a.owned_only = owned_only ? 1 : 0;
+  hipLaunchKernelGGL(k_entry_emit, grid1(nv), dim3(256), 0, st, a, key.p, flag.p);
+  PA_HIP_OR(hipGetLastError(), -1);
+  PA_HIP_OR(scan_count(flag, rank, nv, st, &ne), -1);
+  if (ne <= 0) return 0;
+  PA_HIP_OR(ekey.alloc(ne), -1);
+  PA_HIP_OR(eidx.alloc(ne), -1);
+  hipLaunchKernelGGL(k_entry_compact, grid1(nv), dim3(256), 0, st, nv, key.p, flag.p, rank.p, ekey.p, eidx.p);
+  PA_HIP_OR(hipGetLastError(), -1);
+  PA_HIP_OR(hipStreamSynchronize(st), -1);
+  key.reset(), flag.reset(), rank.reset();  // before the sort takes its buffers
+  // both lid counts guarded against 0 (a matrix without column lids stores
+  // nothing and does not get here): the bits of the largest key of either order
+  const uint64_t nrl = (uint64_t)(A->nrows_lids > 0 ? A->nrows_lids : 1);
+  const uint64_t ncl = (uint64_t)(A->ncols_lids > 0 ? A->ncols_lids : 1);
+  PA_HIP_OR(sort_pairs(ekey, eidx, ne, bits_for(nrl * ncl), st), -1);
+  *ne_out = ne;
+  return 0;
+}
+
+int mat_entry_table(pa_mat* A, const pa_index* rows, hipStream_t st) {
+  if (entry_pairs(A, rows, false, false, A->d_ekey, A->d_eidx, &A->n_entries, st) != 0) return -1;
   A->has_entries = true;
   return 0;
 }
@@ -1165,13 +1185,14 @@ int mat_entry_ids(const pa_mat* A, const pa_index* rows, const pa_index* cols, b
 // ---------------------------------------------------------------------------
 // findnz / nziterator of a PSparseMatrix part (pa_mat_findnz; the filter of
 // gather(A), Interfaces.jl:2671-2687): the stored entries back as (I, J, V)
-// in the parent's storage order, the inverse of pa_mat_from_dcoo.  The entry
-// table's passes with the key of the parent's order — col_lid * nrows_lids +
-// row_lid for a CSC parent (SparseUtils.jl:106-150), row_lid * ncols_lids +
-// col_lid for a CSR parent (254-300) — emit, compact and sort the (key, value
-// index) pairs; k_findnz_write then splits each key into its ids and reads
-// the entry's value from main.val, the one copy every layout is refreshed
-// from.  The pairs are the call's own: the matrix's entry table is neither
+// in the parent's storage order, the inverse of pa_mat_from_dcoo.
+// entry_pairs, the routine that also builds the entry table, gives the
+// (key, value index) pairs sorted by the key of the parent's order —
+// col_lid * nrows_lids + row_lid for a CSC parent (SparseUtils.jl:106-150),
+// row_lid * ncols_lids + col_lid for a CSR parent (254-300);
+// k_findnz_write then splits each key into its ids and reads the entry's
+// value from main.val, the one copy every layout is refreshed from.  The
+// pairs land in the call's own buffers: the matrix's entry table is neither
 // used nor built.
 
 constexpr int kFindnzBlocks = 2048;  // grid of k_findnz_write (8 blocks per CU): kFindnzBlocks * 256 entries per grid pass
@@ -1209,36 +1230,14 @@ int mat_findnz(const pa_mat* A, const pa_index* rows, const pa_index* cols, bool
                CooList& out, hipStream_t st) {
   out.I.reset(), out.J.reset(), out.V.reset();
   out.n = 0;
-  const int64_t nv = A->main.slots + A->n_gnz + A->n_lnz;
-  if (nv <= 0) return 0;
   const int colmajor = A->csr ? 0 : 1;
-  DevBuf<uint64_t> key, ekey;
-  DevBuf<int64_t> flag, rank, eidx;
-  int64_t last[2] = {0, 0};
-  PA_HIP_OR(key.alloc(nv), -1);
-  PA_HIP_OR(flag.alloc(nv), -1);
-  PA_HIP_OR(rank.alloc(nv), -1);
-  const EntrySrc a = {A->main.slots, A->n_gnz, A->n_lnz, A->main.nrows, A->main.nslices, A->ncols_lids, A->n_long,
-                      A->H, A->R, A->main.off, A->main.col, A->d_kind, rows->own_contig ? nullptr : rows->d_oid_to_lid.p,
-                      A->d_ghost_rc, A->d_long_row, A->d_long_ptr, A->d_long_col, A->nrows_lids, colmajor,
-                      owned_only ? 1 : 0};
-  hipLaunchKernelGGL(k_entry_emit, grid1(nv), dim3(256), 0, st, a, key.p, flag.p);
-  PA_HIP_OR(hipGetLastError(), -1);
-  PA_HIP_OR(exclusive_sum(flag, rank, nv, st), -1);
-  PA_HIP_OR(hipMemcpyAsync(&last[0], rank.p + nv - 1, 8, hipMemcpyDeviceToHost, st), -1);
-  PA_HIP_OR(hipMemcpyAsync(&last[1], flag.p + nv - 1, 8, hipMemcpyDeviceToHost, st), -1);
-  PA_HIP_OR(hipStreamSynchronize(st), -1);
-  const int64_t ne = last[0] + last[1];
+  DevBuf<uint64_t> ekey;
+  DevBuf<int64_t> eidx;
+  int64_t ne = 0;
+  if (entry_pairs(A, rows, colmajor != 0, owned_only, ekey, eidx, &ne, st) != 0) return -1;
   if (ne <= 0) return 0;
-  PA_HIP_OR(ekey.alloc(ne), -1);
-  PA_HIP_OR(eidx.alloc(ne), -1);
-  hipLaunchKernelGGL(k_entry_compact, grid1(nv), dim3(256), 0, st, nv, key.p, flag.p, rank.p, ekey.p, eidx.p);
-  PA_HIP_OR(hipGetLastError(), -1);
-  PA_HIP_OR(hipStreamSynchronize(st), -1);
-  key.reset(), flag.reset(), rank.reset();  // before the sort takes its buffers
   const uint64_t nrl = (uint64_t)(A->nrows_lids > 0 ? A->nrows_lids : 1);
   const uint64_t ncl = (uint64_t)(A->ncols_lids > 0 ? A->ncols_lids : 1);
-  PA_HIP_OR(sort_pairs(ekey, eidx, ne, bits_for(nrl * ncl), st), -1);
   PA_HIP_OR(out.I.alloc(ne), -1);
   PA_HIP_OR(out.J.alloc(ne), -1);
   PA_HIP_OR(out.V.alloc(ne * dtype_size(A->dtype)), -1);

@@ -400,18 +400,8 @@ class DeviceVector:
         (the COO constructor).  ids: 1-based lids (Int32 / Int64), or Int64
         gids when ids_global — an Int64 array is then translated to lids in
         place.  ids, vals: host arrays, or both DeviceArray."""
-        n, ib, on_device, ip, keep = _ids_arg(ids, ids_global, writable=ids_global)
-        if on_device != isinstance(vals, DeviceArray):
-            raise TypeError("scatter: ids and vals must both be host arrays or both DeviceArray")
-        if on_device:
-            if vals.dtype != self.dtype or vals.n != n:
-                raise ValueError("scatter: vals must hold one value of the vector's type per id")
-            vp = C.c_void_p(vals.ptr)
-        else:
-            vals = np.ascontiguousarray(vals, dtype=self.dtype).ravel()
-            if len(vals) != n:
-                raise ValueError("scatter: ids and vals must have the same length")
-            vp = vals.ctypes.data_as(C.c_void_p)
+        n, ib, on_device, (ip,), keep = _ids_args(ids_global, ids, writable=ids_global)
+        vp = _vals_arg(vals, n, self.dtype, on_device)
         _lib.call("pa_vec_scatter", self.h, idx.h, _lib.PA_IDS_GLOBAL if ids_global else _lib.PA_IDS_LOCAL, ib,
                   int(op), 1 if zero_first else 0, 1 if on_device else 0, n, ip, vp)
         if keep is not None:  # ids was no contiguous Int64 array: hand the lids back
@@ -421,14 +411,8 @@ class DeviceVector:
         """pa_vec_gather: values[lid(ids[k])] as a host array (ids a host
         array), or into the DeviceArray `out` (ids a DeviceArray).  An absent
         gid reads zero with absent_zero, else it is an error."""
-        n, ib, on_device, ip, _ = _ids_arg(ids, ids_global, writable=False)
-        if on_device:
-            if not isinstance(out, DeviceArray) or out.dtype != self.dtype or out.n != n:
-                raise TypeError("gather: device ids need a DeviceArray `out` of the vector's type, one value per id")
-            op = C.c_void_p(out.ptr)
-        else:
-            out = np.empty(n, dtype=self.dtype)
-            op = out.ctypes.data_as(C.c_void_p)
+        n, ib, on_device, (ip,), _ = _ids_args(ids_global, ids)
+        out, op = _out_arg(out, n, self.dtype, on_device)
         _lib.call("pa_vec_gather", self.h, idx.h, _lib.PA_IDS_GLOBAL if ids_global else _lib.PA_IDS_LOCAL, ib,
                   1 if absent_zero else 0, 1 if on_device else 0, n, ip, op)
         return out
@@ -450,45 +434,61 @@ class DeviceArray:
         self.ptr, self.n, self.dtype, self.owner = int(ptr), int(n), np.dtype(dtype), owner
 
 
-def _ids_arg(ids, ids_global, writable):
-    """(n, index_bytes, on_device, pointer, keep) of an id array: lids cross
-    as Int32 or Int64 as given, gids as Int64.  keep = [the Int64 copy] when
-    `writable` ids (an ndarray) had to be copied, so that the caller can hand
-    the translated ids back."""
-    if isinstance(ids, DeviceArray):
-        if ids.dtype not in (np.dtype(np.int32), np.dtype(np.int64)) or (ids_global and ids.dtype != np.dtype(np.int64)):
-            raise TypeError("ids on the device must be Int64 (gids, lids) or Int32 (lids)")
-        return ids.n, ids.dtype.itemsize, True, C.c_void_p(ids.ptr), None
-    a = np.asarray(ids)
-    if a.size and a.dtype.kind not in "iu":
-        raise TypeError("ids must be integers")
-    want = np.int32 if (a.dtype == np.int32 and not ids_global) else np.int64
-    same = isinstance(ids, np.ndarray) and ids.dtype == want and ids.flags.c_contiguous and (ids.flags.writeable or not writable)
-    b = ids.reshape(-1) if same else np.ascontiguousarray(a, dtype=want).ravel().copy()
-    keep = [b] if (writable and not same and isinstance(ids, np.ndarray) and ids.flags.writeable) else None
-    return b.size, b.dtype.itemsize, False, b.ctypes.data_as(C.c_void_p), keep
-
-
-def _ids_pair(I, J, ids_global):
-    """(n, index_bytes, on_device, pointer of I, pointer of J, keep) of the
-    row and column ids of a matrix access: both cross in one width (Int32
-    only when both are Int32 lids).  keep holds the host copies alive."""
-    if isinstance(I, DeviceArray) != isinstance(J, DeviceArray):
+def _ids_args(ids_global, *ids, writable=False):
+    """(n, index_bytes, on_device, pointers, keep) of the id arrays of a call
+    (one, or the row and column ids of a matrix access): host arrays or all
+    DeviceArray, crossing in one width — gids as Int64, lids as Int32 only
+    when all are Int32.  writable (one array): the call writes into it; keep =
+    [the Int64 copy] when the ndarray could not be passed itself, so that
+    the caller can hand the translated ids back."""
+    dev = [isinstance(x, DeviceArray) for x in ids]
+    if any(dev) != all(dev):
         raise TypeError("I and J must both be host arrays or both DeviceArray")
-    if isinstance(I, DeviceArray):
-        if I.dtype != J.dtype or I.n != J.n:
+    if dev[0]:
+        d = ids[0]
+        if any(x.dtype != d.dtype or x.n != d.n for x in ids):
             raise ValueError("I and J on the device must have one type and one length")
-        n, ib, _, ip, _ = _ids_arg(I, ids_global, writable=False)
-        return n, ib, True, ip, C.c_void_p(J.ptr), None
-    a, b = np.asarray(I), np.asarray(J)
-    if (a.size and a.dtype.kind not in "iu") or (b.size and b.dtype.kind not in "iu"):
+        if d.dtype not in (np.dtype(np.int32), np.dtype(np.int64)) or (ids_global and d.dtype != np.dtype(np.int64)):
+            raise TypeError("ids on the device must be Int64 (gids, lids) or Int32 (lids)")
+        return d.n, d.dtype.itemsize, True, [C.c_void_p(x.ptr) for x in ids], None
+    arrs = [np.asarray(x) for x in ids]
+    if any(a.size and a.dtype.kind not in "iu" for a in arrs):
         raise TypeError("ids must be integers")
-    want = np.int32 if (not ids_global and a.dtype == np.int32 and b.dtype == np.int32) else np.int64
-    a = np.ascontiguousarray(a, dtype=want).ravel()
-    b = np.ascontiguousarray(b, dtype=want).ravel()
-    if a.size != b.size:
+    want = np.int32 if (not ids_global and all(a.dtype == np.int32 for a in arrs)) else np.int64
+    arrs = [np.ascontiguousarray(a, dtype=want).ravel() for a in arrs]
+    if any(a.size != arrs[0].size for a in arrs):
         raise ValueError("I and J must have the same length")
-    return a.size, a.dtype.itemsize, False, a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), (a, b)
+    keep, x = None, ids[0]
+    if writable and not (isinstance(x, np.ndarray) and x.dtype == want and x.flags.c_contiguous and x.flags.writeable):
+        arrs[0] = arrs[0].copy()
+        keep = [arrs[0]] if isinstance(x, np.ndarray) and x.flags.writeable else None
+    return arrs[0].size, arrs[0].dtype.itemsize, False, [a.ctypes.data_as(C.c_void_p) for a in arrs], keep
+
+
+def _vals_arg(vals, n, dtype, on_device):
+    """pointer to the n values of a scatter: a host array converted to dtype,
+    or with ids on the device a DeviceArray of dtype"""
+    if on_device != isinstance(vals, DeviceArray):
+        raise TypeError("scatter: the ids and the values must all be host arrays or all DeviceArray")
+    if on_device:
+        if vals.dtype != dtype or vals.n != n:
+            raise ValueError("scatter: the values must be of the element type, one per id")
+        return C.c_void_p(vals.ptr)
+    vals = np.ascontiguousarray(vals, dtype=dtype).ravel()
+    if len(vals) != n:
+        raise ValueError("scatter: the ids and the values must have the same length")
+    return vals.ctypes.data_as(C.c_void_p)
+
+
+def _out_arg(out, n, dtype, on_device):
+    """(result, pointer) of a gather of n values: a new host array, or with
+    ids on the device the caller's DeviceArray `out`"""
+    if not on_device:
+        out = np.empty(n, dtype=dtype)
+        return out, out.ctypes.data_as(C.c_void_p)
+    if not isinstance(out, DeviceArray) or out.dtype != dtype or out.n != n:
+        raise TypeError("gather: device ids need a DeviceArray `out` of the element type, one value per id")
+    return out, C.c_void_p(out.ptr)
 
 
 class DeviceCOO:
@@ -671,18 +671,8 @@ class DeviceMatrix:
         matrix's rows / cols, or Int64 gids when ids_global; they are left
         unchanged.  I, J, V: host arrays, or all DeviceArray.  A write to an
         entry the pattern does not store is an error."""
-        n, ib, on_device, ip, jp, _keep = _ids_pair(I, J, ids_global)
-        if on_device != isinstance(V, DeviceArray):
-            raise TypeError("scatter: I, J and V must all be host arrays or all DeviceArray")
-        if on_device:
-            if V.dtype != self.dtype or V.n != n:
-                raise ValueError("scatter: V must hold one value of the matrix's type per entry")
-            vp = C.c_void_p(V.ptr)
-        else:
-            V = np.ascontiguousarray(V, dtype=self.dtype).ravel()
-            if len(V) != n:
-                raise ValueError("scatter: I, J and V must have the same length")
-            vp = V.ctypes.data_as(C.c_void_p)
+        n, ib, on_device, (ip, jp), _ = _ids_args(ids_global, I, J)
+        vp = _vals_arg(V, n, self.dtype, on_device)
         _lib.call("pa_mat_scatter", self.h, rows_idx.h, cols_idx.h,
                   _lib.PA_IDS_GLOBAL if ids_global else _lib.PA_IDS_LOCAL, ib, int(op), 1 if on_device else 0, n,
                   ip, jp, vp)
@@ -693,14 +683,8 @@ class DeviceMatrix:
         into the DeviceArray `out` (I, J DeviceArray).  An entry the pattern
         does not store reads zero; an absent gid reads zero with absent_zero,
         else it is an error."""
-        n, ib, on_device, ip, jp, _keep = _ids_pair(I, J, ids_global)
-        if on_device:
-            if not isinstance(out, DeviceArray) or out.dtype != self.dtype or out.n != n:
-                raise TypeError("gather: device ids need a DeviceArray `out` of the matrix's type, one value per entry")
-            op = C.c_void_p(out.ptr)
-        else:
-            out = np.empty(n, dtype=self.dtype)
-            op = out.ctypes.data_as(C.c_void_p)
+        n, ib, on_device, (ip, jp), _ = _ids_args(ids_global, I, J)
+        out, op = _out_arg(out, n, self.dtype, on_device)
         _lib.call("pa_mat_gather", self.h, rows_idx.h, cols_idx.h,
                   _lib.PA_IDS_GLOBAL if ids_global else _lib.PA_IDS_LOCAL, ib, 1 if absent_zero else 0,
                   1 if on_device else 0, n, ip, jp, op)

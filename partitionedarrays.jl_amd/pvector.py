@@ -252,8 +252,14 @@ class PVector(_ExprOps):
         return a
 
 
+def _index_sets(rng: PRange, glob=False):
+    """the device index sets of a range's parts (with their gid tables when glob)"""
+    mk = device_index_gids if glob else device_index
+    return [mk(c, s) for c, s in zip(contexts(rng.partition), rng.partition.parts)]
+
+
 def _idx(v: PVector):
-    return [device_index(c, s).h for c, s in zip(contexts(v.rows.partition), v.rows.partition.parts)]
+    return [x.h for x in _index_sets(v.rows)]
 
 
 def copyto_(a: PVector, b: PVector) -> PVector:
@@ -268,17 +274,11 @@ def copyto_(a: PVector, b: PVector) -> PVector:
     return a
 
 
-def _part_index(v: PVector, glob: bool):
-    """the device index sets of v's parts (with their gid tables when glob)"""
-    mk = device_index_gids if glob else device_index
-    return [mk(c, s) for c, s in zip(contexts(v.rows.partition), v.rows.partition.parts)]
-
-
 def _scatter_parts(v: PVector, I: PData, V: PData, ids, op, zero_first=False):
     if I.part_ids != v.values.part_ids or V.part_ids != v.values.part_ids:
         raise ValueError("PVector(I, V, rows): partitioned data over different parts")
     glob = ids == "global"
-    for dv, x, i, w in zip(v.values.parts, _part_index(v, glob), I.parts, V.parts):
+    for dv, x, i, w in zip(v.values.parts, _index_sets(v.rows, glob), I.parts, V.parts):
         dv.scatter(x, i, w, ids_global=glob, op=op, zero_first=zero_first)
     return v
 
@@ -318,9 +318,15 @@ def add_coo_(v, I: PData, *args, ids="global"):
 def _mat_index(A, glob: bool):
     """per part, the device index sets of A's rows and cols (with their gid
     tables when glob)"""
-    mk = device_index_gids if glob else device_index
-    return [(mk(c, r), mk(c, s))
-            for c, r, s in zip(contexts(A.rows.partition), A.rows.partition.parts, A.cols.partition.parts)]
+    return list(zip(_index_sets(A.rows, glob), _index_sets(A.cols, glob)))
+
+
+def _mapped_ids(ids, gids):
+    """the lids `ids` of a mapped view's range as gids (gids: its lid_to_gid)"""
+    ids = np.asarray(ids).astype(np.int64).ravel()
+    if len(ids) and (ids.min() < 1 or ids.max() > len(gids)):
+        raise _lib.PAError("local_view: a local id is out of range (BoundsError)")
+    return gids[ids - 1]
 
 
 class VectorView:
@@ -340,13 +346,7 @@ class VectorView:
         self.dv, self.idx, self.kind, self.gids = dv, idx, kind, gids
 
     def _ids(self, ids):
-        ids = np.asarray(ids)
-        if self.kind != "mapped":
-            return ids.copy()
-        ids = ids.astype(np.int64).ravel()
-        if len(ids) and (ids.min() < 1 or ids.max() > len(self.gids)):
-            raise _lib.PAError("local_view: a local id is out of range (BoundsError)")
-        return self.gids[ids - 1]
+        return _mapped_ids(ids, self.gids) if self.kind == "mapped" else np.array(ids)
 
     def get(self, ids):
         return self.dv.gather(self.idx, self._ids(ids), ids_global=self.kind != "local",
@@ -379,12 +379,7 @@ class MatrixView:
         self.M, self.ridx, self.cidx, self.kind, self.rgids, self.cgids = M, ridx, cidx, kind, rgids, cgids
 
     def _ids(self, ids, gids):
-        if self.kind != "mapped":
-            return ids
-        ids = np.asarray(ids).astype(np.int64).ravel()
-        if len(ids) and (ids.min() < 1 or ids.max() > len(gids)):
-            raise _lib.PAError("local_view: a local id is out of range (BoundsError)")
-        return gids[ids - 1]
+        return _mapped_ids(ids, gids) if self.kind == "mapped" else ids
 
     def get(self, I, J):
         return self.M.gather(self.ridx, self.cidx, self._ids(I, self.rgids), self._ids(J, self.cgids),
@@ -433,7 +428,7 @@ def global_view(v, rows: PRange = None, cols: PRange = None) -> PData:
         raise TypeError("global_view(a, rows): a PVector has no cols")
     if rows is not None and rows is not v.rows:
         raise NotImplementedError("global_view(a, rows): only for rows === a.rows (Interfaces.jl:2038)")
-    views = [VectorView(dv, x, "global") for dv, x in zip(v.values.parts, _part_index(v, True))]
+    views = [VectorView(dv, x, "global") for dv, x in zip(v.values.parts, _index_sets(v.rows, True))]
     return PData(v.values.backend, v.values.part_ids, views, v.values.shape)
 
 
@@ -451,12 +446,12 @@ def local_view(v, rows: PRange = None, cols: PRange = None) -> PData:
         raise TypeError("local_view(a, rows): a PVector has no cols")
     p = v.values
     if rows is None or rows is v.rows:
-        views = [VectorView(dv, x, "local") for dv, x in zip(p.parts, _part_index(v, False))]
+        views = [VectorView(dv, x, "local") for dv, x in zip(p.parts, _index_sets(v.rows))]
     else:
         if rows.partition.part_ids != p.part_ids:
             raise ValueError("local_view: rows over different parts")
         views = [VectorView(dv, x, "mapped", np.asarray(s.lid_to_gid, dtype=np.int64))
-                 for dv, x, s in zip(p.parts, _part_index(v, True), rows.partition.parts)]
+                 for dv, x, s in zip(p.parts, _index_sets(v.rows, True), rows.partition.parts)]
     return PData(p.backend, p.part_ids, views, p.shape)
 
 

@@ -164,9 +164,12 @@ def neighbours27(grid, g):
 class Case2:
     """A 27-point operator over two parts as an FE assembly leaves it: each
     part stores its owned rows and the rows of its ghost nodes (the plane of
-    the other part next to the interface), plus two long owned rows."""
+    the other part next to the interface), plus two long owned rows.
+    parent: "csc", or the Bi of SparseMatrixCSR{Bi} parents; shuffle_row_lids:
+    the lids of rows in a random order, owned and ghost lids mixed (those of
+    cols stay owned-then-ghost, which the pattern and delta16 slices need)."""
 
-    def __init__(self, pamd, be, dtype, f32_rows=0, seed=29):
+    def __init__(self, pamd, be, dtype, f32_rows=0, seed=29, parent="csc", shuffle_row_lids=False):
         rng = np.random.default_rng(seed)
         self.dtype, self.f32_rows = dtype, f32_rows
         self.parts = parts = be.get_part_ids(2)
@@ -187,14 +190,19 @@ class Case2:
             Jg.append(j[o])
         pamd.add_gids_(rows, pdata(parts, Ig))
         pamd.add_gids_(cols, pdata(parts, Jg))
+        if shuffle_row_lids:
+            order = [rng.permutation(s.num_lids) for s in rows.partition.parts]
+            rows = pamd.prange_from_partition(n, pdata(parts, [
+                pamd.IndexSet(s.part, s.lid_to_gid[o], s.lid_to_part[o]) for s, o in zip(rows.partition.parts, order)]))
         self.rows, self.cols = rows, cols
         V0 = [entries(dtype, len(i), rng) for i in Ig]
         with knob(pamd, "f32_rows", f32_rows):
             self.A = pamd.PSparseMatrix.from_coo(pdata(parts, [i.copy() for i in Ig]),
                                                  pdata(parts, [j.copy() for j in Jg]), pdata(parts, V0), rows, cols,
-                                                 ids="global")
-        # the host restatement of sparse(I, J, V): the parents' patterns
-        self.csc = [pamd.compresscoo(r.to_lids(i), c.to_lids(j), v, r.num_lids, c.num_lids)
+                                                 ids="global", init=None if parent == "csc" else pamd.csr_init(parent))
+        # the host restatement of sparse(I, J, V) / sparsecsr: the parents' patterns
+        compress = pamd.compresscoo if parent == "csc" else pamd.csr_init(parent)
+        self.csc = [compress(r.to_lids(i), c.to_lids(j), v, r.num_lids, c.num_lids)
                     for r, c, i, j, v in zip(rows.partition.parts, cols.partition.parts, Ig, Jg, V0)]
         self.pat = [pattern_of(M) for M in self.csc]
         # shuffled triplets: every stored entry once, and as many again drawn with repetition
@@ -621,3 +629,62 @@ def test_the_entry_table_is_built_by_the_first_view_call(be, pamd):
     assert ghost_nnz > 0 and info["long_rows"] > 0
     assert M0.entry_table() == (info["nnz"] + ghost_nnz, 16 * (info["nnz"] + ghost_nnz))
     assert M1.entry_table() == (0, 0)  # a table per matrix part
+
+
+# ---------------------------------------------------------------------------
+# 6. the entry table and findnz: one pair-building routine, no shared state
+
+def _findnz(pamd, c, p, all_rows, ids_global):
+    """findnz of part p of the case's matrix: (I, J, V) on the host"""
+    ctx = pamd.device.contexts(c.rows.partition)[p]
+    index = pamd.device.device_index_gids if ids_global else pamd.device.device_index
+    r, cl = index(ctx, c.rows.partition.parts[p]), index(ctx, c.cols.partition.parts[p])
+    return c.A.values.parts[p].findnz(r, cl, all_rows=all_rows, ids_global=ids_global).download()
+
+
+def _same_coo(a, b):
+    return np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and same_bits(a[2], b[2])
+
+
+@pytest.mark.parametrize("parent", ["csc", 1], ids=["csc", "csr"])
+@pytest.mark.parametrize("dtype,f32_rows", [(np.float32, 4), (np.float64, 0)], ids=["float32", "float64"])
+def test_entry_table_and_findnz_share_no_state(be, pamd, dtype, f32_rows, parent):
+    """findnz before, between and after the view calls that build the entry
+    table: neither changes what the other gives, in either order."""
+    c = Case2(pamd, be, dtype, f32_rows, seed=61, parent=parent, shuffle_row_lids=True)
+    F = []
+    for p, (M, s) in enumerate(zip(c.A.values.parts, c.rows.partition.parts)):
+        info = M.info()
+        print(p, {k: info[k] for k in ("nrows", "nnz", "nslices", "long_rows", "delta16_slices")}, M.csc_nnz)
+        # what the matrix must hold for the passes to meet every kind of value index
+        assert np.any(np.diff(s.oid_to_lid) != 1) and s.num_hids > 0  # owned lids not contiguous
+        assert M.csc_nnz - info["nnz"] > 0                            # stored ghost rows
+        assert info["long_rows"] > 0
+        assert dtype != np.float32 or info["delta16_slices"] > 0
+        # 1. findnz builds no table
+        F0 = _findnz(pamd, c, p, True, False)
+        assert len(F0[0]) == M.csc_nnz and M.entry_table() == (0, 0)
+        # 2. the first view call does, and reads the same values
+        view = pamd.local_view(c.A, c.rows, c.cols).parts[p]
+        assert same_bits(view.get(F0[0], F0[1]), F0[2])
+        table = M.entry_table()
+        assert table == (len(F0[0]), 16 * len(F0[0]))
+        # 3. findnz again: the same, and the table as it was
+        assert _same_coo(_findnz(pamd, c, p, True, False), F0) and M.entry_table() == table
+        # 4. a write through the table, read back by findnz over the owned rows
+        view.add_(F0[0], F0[1], np.ones(len(F0[0]), dtype))
+        own = s.lid_to_part[F0[0] - 1] == s.part
+        assert 0 < own.sum() < len(own)
+        F4 = _findnz(pamd, c, p, False, False)
+        assert _same_coo(F4, (F0[0][own], F0[1][own], F0[2][own] + dtype(1)))
+        # 5. and with global ids
+        gids = (s.lid_to_gid[F4[0] - 1], c.cols.partition.parts[p].lid_to_gid[F4[1] - 1], F4[2])
+        assert _same_coo(_findnz(pamd, c, p, False, True), gids) and M.entry_table() == table
+        F.append(F0)
+    # a fresh matrix, the table first: findnz gives the same
+    c = Case2(pamd, be, dtype, f32_rows, seed=61, parent=parent, shuffle_row_lids=True)
+    for p, (M, F0) in enumerate(zip(c.A.values.parts, F)):
+        assert M.entry_table() == (0, 0)
+        assert same_bits(pamd.local_view(c.A, c.rows, c.cols).parts[p].get(F0[0], F0[1]), F0[2])
+        assert M.entry_table() == (len(F0[0]), 16 * len(F0[0]))
+        assert _same_coo(_findnz(pamd, c, p, True, False), F0)
