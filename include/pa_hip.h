@@ -85,7 +85,14 @@ int pa_device_count(int* count);
  * "halo_direct" 1: mul! over parts sharing a stream pair reads every ghost
  *               straight from its owner's x on the compute stream (no
  *               pack, no cross-stream event; default), 0: pack + pull on
- *               the comm stream overlapped with the interior slices;
+ *               the comm stream overlapped with the interior slices.  The
+ *               direct pull reads the senders' x while it writes the
+ *               receivers', so it is taken only when no part of the call
+ *               sends a lid that it also receives (true of every exchanger
+ *               made from a PRange: owned lids sent, ghosts received);
+ *               otherwise the call packs first, as with 0.  An exchanger
+ *               that receives on owned lids also makes mul! run the interior
+ *               slices after the halo instead of beside it;
  * "halo_transport" 0 (default): parts of one process exchange by device
  *               reads/copies, except parts whose communicator came from
  *               pa_comm_init_all (RCCL, per context); 1: RCCL send/recv for

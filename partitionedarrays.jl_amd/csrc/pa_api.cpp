@@ -986,7 +986,13 @@ int build_pull(int i, int n, pa_xchg* const xg[], const LocalSet& L, int dtype, 
 // Direct pull table of receiver i for a grouped mul! over the n parts of
 // the call (all local, one device): receive slot p of segment k (sender q at
 // call position j) reads x_j at the lid q lists for this part in its
-// lids_snd.  ok = false when a sender is not in the call.
+// lids_snd.  ok = false when a sender is not in the call, or when a sender
+// sends a lid that it also receives (pa_xchg::snd_in_rcv, found once when the
+// exchanger is created): the one pull launch of the call would read that lid
+// of the sender's x while other blocks of it write it, and which value
+// travels would depend on block timing; the reference sends the old one
+// (every part packs before any unpacks), as the packed pull does.  An
+// exchanger made from a PRange sends owned lids and receives ghosts: direct.
 int build_direct(int i, int n, pa_xchg* const xg[], const LocalSet& L) {
   pa_xchg* X = xg[i];
   pa_pull& P = X->direct;
@@ -1004,7 +1010,7 @@ int build_direct(int i, int n, pa_xchg* const xg[], const LocalSet& L) {
     const int j = L.find(r.parts[k]);
     if (j < 0) return 0;
     const pa_xchg* Q = xg[j];
-    if ((int64_t)Q->h_lids_snd.size() != Q->snd.n) return 0;
+    if ((int64_t)Q->h_lids_snd.size() != Q->snd.n || Q->snd_in_rcv) return 0;
     const int64_t cnt = r.ptrs[k + 1] - r.ptrs[k];
     int m = -1;
     if (peer_segment(Q, 0, X->ctx->part, cnt, &m)) return -1;
@@ -1995,6 +2001,8 @@ int pa_index_create(pa_ctx* c, int64_t nlids, int64_t noids, const int32_t* oid_
   CHECK_ARG(nlids < (int64_t)INT32_MAX, "index set larger than Int32 lids");
   HIPC(hipSetDevice(c->device));
   auto I = std::make_unique<pa_index>();
+  static std::atomic<uint64_t> next_id{1};
+  I->id = next_id.fetch_add(1);
   I->ctx = c;
   I->nlids = nlids;
   I->noids = noids;
@@ -2153,6 +2161,12 @@ int pa_xchg_create(pa_ctx* c, int32_t n_rcv, const int32_t* parts_rcv, const int
   HIPC(X->rcv.lids.upload(hr));
   HIPC(X->snd.lids.upload(hs));
   X->h_lids_snd = hs;
+  X->h_lids_rcv = hr;
+  {
+    std::vector<char> received(X->max_lid + 1, 0);
+    for (int32_t l : hr) received[l] = 1;
+    for (int32_t l : hs) X->snd_in_rcv = X->snd_in_rcv || received[l];
+  }
   if (X->rcv.n) HIPC(X->rcv.buf.alloc(X->rcv.n * 16));
   if (X->snd.n) HIPC(X->snd.buf.alloc(X->snd.n * 16));
   if (build_plan(hr, &X->rcv.plan) || build_plan(hs, &X->snd.plan)) return -1;
@@ -3563,6 +3577,7 @@ struct SpmvCall {
   CGState* const* dot_tail;        // the fold of the dot ends in the device CG's α (one part per process)
   std::vector<hipEvent_t*> tslot;  // per part: the four timing events of this call (null: not timed)
   const CGFuse* fz;
+  bool halo_first;  // the halo also writes owned lids of x (halo_writes_owned): the interior slices run after it
 
   const int32_t* ymap(int i) const { return y_idx[i]->own_contig ? nullptr : y_idx[i]->d_oid_to_lid; }
 
@@ -3594,6 +3609,22 @@ struct SpmvCall {
       launch_fold(dt == PA_C64 || dt == PA_C128, nbp, M->d_dotp, c->d_fold, c->d_result, c->d_ticket, st);
   }
 };
+
+// Whether X's forward halo writes an owned lid of the index set of x.  An
+// exchanger made from a PRange receives ghosts only, which the interior
+// slices never read, so they overlap with the halo; PRange(ngids, partition,
+// exchanger) accepts any exchanger, and one that receives on owned lids
+// changes what the interior slices read: mul! then runs them after the halo.
+// One host pass per (exchanger, index set), remembered on the exchanger.
+static bool halo_writes_owned(pa_xchg* X, const pa_index* idx) {
+  if (!idx) return false;
+  if (X->own_key != idx->id) {
+    X->rcv_owned = false;
+    for (int32_t l : X->h_lids_rcv) X->rcv_owned = X->rcv_owned || (l < idx->nlids && idx->h_lid_to_ohid[l] > 0);
+    X->own_key = idx->id;
+  }
+  return X->rcv_owned;
+}
 
 // The grouped path applies when every part of the call shares one stream
 // pair (pa_ctx_create_shared: same device, one in-order chain) and every
@@ -3658,7 +3689,11 @@ static int spmv_grouped(const SpmvCall& C, bool direct) {
   if (dmark && (mark(0) || mark(1))) return -1;
   if (any_x && direct) {
     // every ghost of x straight from its owner's x, in stream order before
-    // the slices (owned values are only read, ghosts only written)
+    // the slices.  One launch reads the senders' x while it writes the
+    // receivers': no lid that a part sends may be one that it receives
+    // (owned values only read, ghosts only written, as in every exchanger
+    // made from a PRange); build_direct turns any other exchanger away and
+    // the packed pull below runs, which packs first
     void** bases = direct_bases(c0, n, x);
     if (!bases) return -1;
     PullGroup qg{};
@@ -3789,6 +3824,8 @@ static int spmv_grouped(const SpmvCall& C, bool direct) {
     }
     // interior slices (no ghost column): overlap with the pulls on the comm stream
     constexpr SliceKind kInteriorOrder[] = {kPattern, kTriple, kDelta16, kInt32};
+    // (a halo that writes owned lids too, halo_writes_owned: no slice beside it)
+    if (any_x && !direct && C.halo_first) HIPC(hipStreamWaitEvent(sm, c0->ev_recvd, 0));
     for (SliceKind k : kInteriorOrder) launch_kind(kInterior, k, k == kPattern && side_tailed);
     if (!dmark && mark(1)) return -1;
     if (any_x && !direct) HIPC(hipStreamWaitEvent(sm, c0->ev_recvd, 0));
@@ -3992,8 +4029,10 @@ static int spmv_impl(int n, pa_mat* const A[], pa_vec* const y[], const pa_index
     }
     tslot[i] = &c->tev[4 * c->tn];
   }
+  bool halo_first = false;
+  for (int i = 0; i < n && any_x && x_idx; ++i) halo_first = halo_first || halo_writes_owned(xg[i], x_idx[i]);
   const SpmvCall C{n, A, y, y_idx, x, xg, any_x, dt, has_alpha, bmode, alpha, beta, std::move(dotp), want_dot,
-                   dot_tail, std::move(tslot), fz};
+                   dot_tail, std::move(tslot), fz, halo_first};
   if (grouped) return spmv_grouped(C, gmode == 2);
 
   auto pack = [&](int i) -> int {
@@ -4008,7 +4047,8 @@ static int spmv_impl(int n, pa_mat* const A[], pa_vec* const y[], const pa_index
     HIPC(hipSetDevice(c->device));
     if (C.tslot[i]) HIPC(hipEventRecord(C.tslot[i][0], c->s_main));
     // interior slices (no ghost column): overlap with the halo transport
-    if (launch_phase(C, kInterior, i, c->s_main)) return -1;
+    // (halo_first: it writes owned lids too, boundary(i) runs them after it)
+    if (!C.halo_first && launch_phase(C, kInterior, i, c->s_main)) return -1;
     if (C.tslot[i]) HIPC(hipEventRecord(C.tslot[i][1], c->s_main));
     return 0;
   };
@@ -4023,6 +4063,7 @@ static int spmv_impl(int n, pa_mat* const A[], pa_vec* const y[], const pa_index
     }
     if (C.tslot[i]) HIPC(hipEventRecord(C.tslot[i][2], c->s_main));
     // slices reading ghosts and the side rows (after the halo)
+    if (C.halo_first && launch_phase(C, kInterior, i, c->s_main)) return -1;
     if (launch_phase(C, kBoundary, i, c->s_main)) return -1;
     C.finish_part(i, c->s_main);
     if (C.tslot[i]) HIPC(hipEventRecord(C.tslot[i][3], c->s_main));

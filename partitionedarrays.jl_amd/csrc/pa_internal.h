@@ -470,6 +470,7 @@ inline hipError_t download(std::vector<T>& h, const T* d, size_t n, hipStream_t 
 
 struct pa_index {
   pa_ctx* ctx = nullptr;
+  uint64_t id = 0;           // unique per index set of the process (cache keys)
   int64_t nlids = 0, noids = 0, nhids = 0;
   bool own_contig = true;    // oid_to_lid == 0..noids-1 (0-based)
   bool ghost_contig = true;  // hid_to_lid == noids..nlids-1
@@ -542,7 +543,17 @@ struct pa_xchg {
   // receive slot p reads x of the call's part bid[p] at lid elem[p] (the
   // sender's snd.lids entry), no pack, no send buffer, no cross-stream event
   pa_pull direct;
-  std::vector<int32_t> h_lids_snd;             // 0-based host copy (vector exchangers)
+  std::vector<int32_t> h_lids_snd;             // 0-based host copies (vector exchangers)
+  std::vector<int32_t> h_lids_rcv;
+  // a lid of lids_snd is also in lids_rcv (legal: every part packs before any
+  // unpacks, the old value travels): the direct pull, which reads the
+  // senders' x while it writes the receivers', is not taken (build_direct)
+  bool snd_in_rcv = false;
+  // lids_rcv names an owned lid of the index set with id own_key (0: not
+  // looked at yet): the halo then also writes what the interior slices read,
+  // and mul! runs them after it (halo_writes_owned)
+  uint64_t own_key = 0;
+  bool rcv_owned = false;
   // forward (dir 0, exchange!): snd's slots travel to the neighbours' rcv;
   // reverse (dir 1, assemble!): rcv's slots travel to the neighbours' snd
   pa::XchgSide rcv, snd;
