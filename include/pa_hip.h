@@ -50,6 +50,7 @@ typedef struct pa_xchg pa_xchg;
 typedef struct pa_vec pa_vec;
 typedef struct pa_mat pa_mat;
 typedef struct pa_coo pa_coo;
+typedef struct pa_table pa_table; /* one part's Table: rows of any length */
 typedef struct pa_event pa_event; /* completion of one call's work for one part */
 
 /* ---- errors / library info ------------------------------------------- */
@@ -808,6 +809,59 @@ int pa_event_wait(pa_event* ev);
 int pa_ctx_wait_event(pa_ctx* ctx, const pa_event* ev);
 /* Frees the handle; legal while its work is pending (the work goes on).   */
 int pa_event_destroy(pa_event* ev);
+
+/* ---- tables: exchange!(combine, values::AbstractPData{<:Table}, exchanger) --
+ * One part's Table (Helpers.jl:63-94) on the device: row lid holds the data
+ * entries ptrs[lid] .. ptrs[lid+1]-1, any number of them (the dof ids of a
+ * cell, the unknowns of a node).  pa_table_create takes the nrows+1 1-based
+ * Int32 ptrs from the host (ptrs_on_device = 0; consumed before the call
+ * returns) or from the context's device (1; checked by a kernel): the first
+ * must be 1 and they must not decrease, anything else is an error and
+ * nothing is handed out.  The data (ptrs[nrows+1]-1 values of dtype, zero at
+ * first) are reached through pa_table_data: a pa_vec view that the table
+ * owns — pa_vec_upload / _download / _device_ptr / _fill work on it, and it
+ * must not be destroyed (it goes with pa_table_destroy).  ptrs are immutable
+ * after creation.  pa_table_info: the rows and the data entries.
+ *
+ * pa_table_exchange_all is the reference's Table exchange (Interfaces.jl:
+ * 891-961) for the n local parts: the exchanger derived from xg[i] and the
+ * table's ptrs (_table_exchanger / _table_lids_snd, 920-961: every lid
+ * replaced by its row's data positions) drives the vector exchange over the
+ * data.  The derivation runs on the device: the expanded
+ * lid lists and the ordered combine plans are never built on or copied to the
+ * host, which reads back one offset per neighbour.  A table keeps the derived
+ * exchanger per base exchanger, so repeated exchanges of one table derive it
+ * once.  op / reverse as pa_exchange_all (contributions to one data entry are
+ * combined in the reference's receive-buffer order, bit-exact); zero_sent as
+ * pa_mat_exchange_all: afterwards the data of the rows the transfer left
+ * from are +0.0.  pa_table_exchange_all_async: the same with the event
+ * semantics of pa_exchange_all_async (after, done); the derivation itself, on
+ * a table's first call with an exchanger, completes before the call returns.
+ *
+ * Checks, all before any value moves (the tables are left as they were):
+ * null handles, a table and an exchanger of different contexts, element
+ * types that differ across parts and nrows smaller than the exchanger's
+ * largest lid are errors raised before any allocation.  The expanded slots
+ * of a side must fit Int32, as the reference's Table ptrs do.  For every
+ * edge between two parts of the call the sender's and the receiver's
+ * expanded segment lengths are compared; a difference is an error naming
+ * both parts and both counts (the reference's @check on the segment sizes,
+ * SequentialBackend.jl:187).  With a peer in another process the lengths are
+ * the caller's contract, as the message sizes of MPI are in the reference:
+ * both sides must hold rows of equal lengths for every slot pair; no sizes
+ * are negotiated.                                                          */
+int pa_table_create(pa_ctx* ctx, int dtype, int64_t nrows, const int32_t* ptrs,
+                    int ptrs_on_device, pa_table** out);
+int pa_table_destroy(pa_table* t);
+int pa_table_data(pa_table* t, pa_vec** data);
+int pa_table_info(const pa_table* t, int64_t* nrows, int64_t* ndata);
+/* the nrows+1 1-based ptrs as the device holds them, into a host array */
+int pa_table_ptrs(const pa_table* t, int32_t* ptrs);
+int pa_table_exchange_all(int n, pa_table* const tables[], pa_xchg* const xg[],
+                          int op, int reverse, int zero_sent);
+int pa_table_exchange_all_async(int n, pa_table* const tables[], pa_xchg* const xg[],
+                                int op, int reverse, int zero_sent,
+                                pa_event* const after[], pa_event* done[]);
 
 /* dot(a,b) (Interfaces.jl:1985-1992) → sum over parts, folded in part
  * order as reduce(+, …; init=0) (Interfaces.jl:221-238).  result: host

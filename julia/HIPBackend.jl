@@ -584,6 +584,106 @@ end
 async_assemble!(a::HIPMatrix{T}, t0::AbstractPData=PartitionedArrays._empty_tasks(a.exchanger.parts_rcv)) where {T<:DeviceEltype} =
   async_assemble!(+, a, t0)
 
+# ---- exchange!([combine_op,] values::AbstractPData{<:Table}, exchanger) -----
+# (Interfaces.jl:891-961) for HIP parts: rows of any length per lid.  Each
+# part's Table gets a pa_table (created once per ptrs Vector: a Table's ptrs
+# do not change) whose derived exchanger the library builds on the device and
+# keeps; the data goes up before the call and comes back in the part's task.
+# Int32 / Int64 data (dof ids) travel as the bits of Float32 / Float64 and can
+# only be replaced.
+mutable struct TableMirror
+  h::Ptr{Cvoid}      # pa_table
+  data::Ptr{Cvoid}   # the pa_vec view of its data (owned by the table)
+end
+function _free_table(m::TableMirror)
+  m.h == C_NULL || ccall((:pa_table_destroy, libpa), Cint, (Ptr{Cvoid},), m.h)
+  m.h = C_NULL
+end
+const TABLE_MIRRORS = Dict{UInt,Tuple{WeakRef,TableMirror}}()  # a Table's ptrs Vector → its pa_table
+const TableEltype = Union{DeviceEltype,Int32,Int64}
+table_carrier(::Type{T}) where {T<:DeviceEltype} = T
+table_carrier(::Type{Int32}) = Float32
+table_carrier(::Type{Int64}) = Float64
+
+function _table_sizes(m::TableMirror)
+  nr = Ref{Int64}(0); nd = Ref{Int64}(0)
+  check(ccall((:pa_table_info, libpa), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), m.h, nr, nd))
+  Int(nr[]), Int(nd[])
+end
+"""the ptrs the device holds for a table (1-based), for checks against the host's"""
+function _table_ptrs(m::TableMirror)
+  p = Vector{Int32}(undef, _table_sizes(m)[1] + 1)
+  check(ccall((:pa_table_ptrs, libpa), Cint, (Ptr{Cvoid}, Ptr{Int32}), m.h, p))
+  p
+end
+
+function _table_handle(ctx::PartCtx, t::Table{T}) where {T<:TableEltype}
+  m = _mirror(TABLE_MIRRORS, t.ptrs)
+  if m !== nothing && _table_sizes(m) != (length(t.ptrs) - 1, length(t.data))
+    m = nothing   # the ptrs Vector was resized in place: a new table (the stale one is freed below)
+  end
+  if m === nothing
+    p32 = convert(Vector{Int32}, t.ptrs)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:pa_table_create, libpa), Cint,
+                (Ptr{Cvoid}, Cint, Int64, Ptr{Int32}, Cint, Ref{Ptr{Cvoid}}),
+                ctx.h, dtype_code(table_carrier(T)), length(p32) - 1, p32, 0, out))
+    d = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:pa_table_data, libpa), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}), out[], d))
+    m = _set_mirror!(TABLE_MIRRORS, t.ptrs, TableMirror(out[], d[]), _free_table)
+  end
+  check(ccall((:pa_vec_upload, libpa), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64), m.data, t.data, length(t.data)))
+  m
+end
+
+_table_op(::typeof(PartitionedArrays._replace), ::Type) = Cint(0)
+_table_op(::typeof(+), ::Type{T}) where {T<:DeviceEltype} = Cint(1)
+_table_op(::typeof(+), ::Type{T}) where {T<:Integer} =
+  error("exchange!(+, Table): integer tables travel as bit patterns and cannot be added on the device")
+_table_op(op, ::Type) = error("exchange!(combine_op, Table) on HIP parts: combine_op must be replace or +")
+
+function _table_handles(values::HIPData{<:Table}, exchanger::Exchanger)
+  ms = [_table_handle(values.ctxs[i], values.parts[i]) for i in eachindex(values.parts)]
+  xg = [_xchg_handle(values.ctxs[i], exchanger, i) for i in eachindex(values.parts)]
+  ms, convert(Vector{Ptr{Cvoid}}, [m.h for m in ms]), xg
+end
+function _table_download(m::TableMirror, t::Table)
+  check(ccall((:pa_vec_download, libpa), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64), m.data, t.data, length(t.data)))
+end
+
+# the blocking form in compute-stream order (no task), any (op, reverse, zero_sent)
+function _table_exchange_all(values::HIPData{<:Table{T}}, exchanger::Exchanger, op::Integer, rev::Integer,
+                             zero_sent::Integer) where {T<:TableEltype}
+  ms, tb, xg = _table_handles(values, exchanger)
+  check(ccall((:pa_table_exchange_all, libpa), Cint,
+              (Cint, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Cint, Cint, Cint), length(tb), tb, xg, op, rev, zero_sent))
+  foreach(_table_download, ms, values.parts)
+  values
+end
+
+function async_exchange!(combine_op, values::HIPData{<:Table{T}}, exchanger::Exchanger,
+                         t0::AbstractPData=PartitionedArrays._empty_tasks(exchanger.parts_rcv)) where {T<:TableEltype}
+  op = _table_op(combine_op, T)
+  ms, tb, xg = _table_handles(values, exchanger)
+  after, holders = _after(t0)
+  done = fill(C_NULL, length(tb))
+  GC.@preserve holders check(ccall((:pa_table_exchange_all_async, libpa), Cint,
+              (Cint, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Cint, Cint, Cint, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}),
+              length(tb), tb, xg, op, 0, 0, after, done))
+  # a part's task waits for its event, then brings the data back into the host Table
+  tasks = map(eachindex(done)) do i
+    ev = EventHolder(done[i])
+    m, t = ms[i], values.parts[i]
+    task = @task begin
+      check(ccall((:pa_event_wait, libpa), Cint, (Ptr{Cvoid},), ev.h))
+      _table_download(m, t)
+    end
+    TASK_EVENTS[task] = ev
+    task
+  end
+  HIPData(tasks, values.ctxs, values.backend)
+end
+
 # fillstored!(a, v) (Interfaces.jl:2127-2132) on the device copies; the host
 # parts are refreshed on their next generic use (sync_host!)
 function LinearAlgebra.fillstored!(a::HIPMatrix{T}, v) where {T<:DeviceEltype}

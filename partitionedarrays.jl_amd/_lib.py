@@ -141,6 +141,14 @@ _SIGS = {
                               C.POINTER(_p), C.POINTER(_p)],
     "pa_mat_exchange_all_async": [C.c_int, C.POINTER(_p), C.POINTER(_p), C.c_int, C.c_int, C.c_int, C.POINTER(_p),
                                   C.POINTER(_p)],
+    "pa_table_create": [_p, C.c_int, C.c_int64, _p, C.c_int, C.POINTER(_p)],
+    "pa_table_destroy": [_p],
+    "pa_table_data": [_p, C.POINTER(_p)],
+    "pa_table_info": [_p, _i64p, _i64p],
+    "pa_table_ptrs": [_p, _i32p],
+    "pa_table_exchange_all": [C.c_int, C.POINTER(_p), C.POINTER(_p), C.c_int, C.c_int, C.c_int],
+    "pa_table_exchange_all_async": [C.c_int, C.POINTER(_p), C.POINTER(_p), C.c_int, C.c_int, C.c_int, C.POINTER(_p),
+                                    C.POINTER(_p)],
     "pa_event_record": [_p, C.POINTER(_p)],
     "pa_event_query": [_p, C.POINTER(C.c_int)],
     "pa_event_wait": [_p],

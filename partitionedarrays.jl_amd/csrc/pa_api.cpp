@@ -4222,9 +4222,11 @@ int event_create(int device, pa_event** out) {
 // work all goes to its comm stream: the three waits (everything enqueued on
 // the context so far; after[i]; the earlier users of the exchanger buffers),
 // the pack, the transport, the unpack, tail(i, s_comm), and done[i] behind it.
+// pull = false: local segments by staging copies whatever halo_pull says (the
+// derived exchangers of tables, which keep no host lists for a pull table).
 int exchange_async(int n, pa_vec* const v[], pa_xchg* const xg[], const pa_index* const idx[], int op, int dir,
                    int zero_ghosts, pa_event* const after[], const std::function<int(int, hipStream_t)>& tail,
-                   pa_event* done[]) {
+                   pa_event* done[], bool pull = true) {
   const int dt = v[0]->dtype;
   for (int i = 0; i < n; ++i) done[i] = nullptr;
   auto issue = [&]() -> int {
@@ -4244,7 +4246,7 @@ int exchange_async(int n, pa_vec* const v[], pa_xchg* const xg[], const pa_index
       if (exchange_pack(i, v, xg, dir, xg[i]->ctx->s_comm)) return -1;
     HIPC(hipGetLastError());
     bool pulled = false;
-    if (transport(n, xg, dt, dir, op, v, &pulled)) return -1;
+    if (transport(n, xg, dt, dir, op, pull ? v : nullptr, &pulled)) return -1;
     for (int i = 0; i < n; ++i) {
       pa_ctx* c = xg[i]->ctx;
       if (exchange_unpack(i, v, xg, idx, op, dir, pulled, zero_ghosts, c->s_comm)) return -1;
@@ -4356,6 +4358,199 @@ int pa_event_destroy(pa_event* ev) {
     if (e) (void)hipEventDestroy(e);
   delete ev;
   return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Tables: exchange!(combine, values::AbstractPData{<:Table}, exchanger)
+// (Interfaces.jl:891-961).
+int pa_table_create(pa_ctx* c, int dtype, int64_t nrows, const int32_t* ptrs, int ptrs_on_device, pa_table** out) {
+  CHECK_ARG(out, "null argument");
+  *out = nullptr;
+  CHECK_ARG(c && ptrs, "null argument");
+  CHECK_ARG(valid_dtype(dtype), "invalid dtype");
+  CHECK_ARG(nrows >= 0 && nrows < INT32_MAX, "Table: the number of rows must be in 0 .. 2^31-2");
+  CHECK_ARG(ptrs_on_device == 0 || ptrs_on_device == 1, "invalid ptrs_on_device");
+  const char* first = "Table: ptrs[1] must be 1";
+  const char* order = "Table: ptrs must not decrease";
+  std::vector<int32_t> h;
+  if (!ptrs_on_device) {  // checked before anything is allocated
+    CHECK_ARG(ptrs[0] == 1, first);
+    h.resize(nrows + 1);
+    for (int64_t i = 0; i <= nrows; ++i) {
+      CHECK_ARG(i == 0 || ptrs[i] >= ptrs[i - 1], order);
+      h[i] = ptrs[i] - 1;
+    }
+  }
+  HIPC(hipSetDevice(c->device));
+  auto T = std::make_unique<pa_table>();
+  T->ctx = c;
+  T->dtype = dtype;
+  T->nrows = nrows;
+  if (ptrs_on_device) {
+    HIPC(T->t.alloc(nrows + 1));
+    int bad = 0;
+    HIPC(table_ptrs(nrows, ptrs, T->t, &bad, &T->ndata, c->s_main));
+    CHECK_ARG(!(bad & 1), first);
+    CHECK_ARG(!(bad & 2), order);
+  } else {
+    HIPC(T->t.upload(h));
+    T->ndata = h[nrows];
+  }
+  if (pa_vec_create(c, dtype, T->ndata, &T->data)) return -1;
+  *out = T.release();
+  return 0;
+}
+
+int pa_table_destroy(pa_table* T) {
+  if (!T) return 0;
+  (void)hipSetDevice(T->ctx->device);
+  (void)hipStreamSynchronize(T->ctx->s_comm);  // an async exchange may still use the derived exchangers
+  pa_vec_destroy(T->data);                     // waits for the compute stream
+  delete T;
+  return 0;
+}
+
+int pa_table_data(pa_table* T, pa_vec** data) {
+  CHECK_ARG(T && data, "null argument");
+  *data = T->data;
+  return 0;
+}
+
+int pa_table_info(const pa_table* T, int64_t* nrows, int64_t* ndata) {
+  CHECK_ARG(T, "null table");
+  if (nrows) *nrows = T->nrows;
+  if (ndata) *ndata = T->ndata;
+  return 0;
+}
+
+int pa_table_ptrs(const pa_table* T, int32_t* ptrs) {
+  CHECK_ARG(T && ptrs, "null argument");
+  pa_ctx* c = T->ctx;
+  HIPC(hipSetDevice(c->device));
+  HIPC(hipMemcpyAsync(ptrs, T->t, (size_t)(T->nrows + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, c->s_main));
+  HIPC(hipStreamSynchronize(c->s_main));
+  for (int64_t i = 0; i <= T->nrows; ++i) ptrs[i] += 1;
+  return 0;
+}
+
+namespace {
+
+// the exchanger of T derived from X (cached on T by X's id)
+int table_plan(pa_table* T, const pa_xchg* X, pa_xchg** out) {
+  for (auto& p : T->plans)
+    if (p.first == X->id) {
+      *out = p.second.get();
+      return 0;
+    }
+  pa_ctx* c = T->ctx;
+  HIPC(hipSetDevice(c->device));
+  auto D = std::make_unique<pa_xchg>();
+  D->ctx = c;
+  D->id = g_xchg_next_id++;
+  D->snd_in_rcv = true;  // no host lists: never a direct-pull sender
+  for (int dir = 0; dir < 2; ++dir) {
+    int64_t total = 0;
+    hipError_t e = hipSuccess;
+    const int rc = table_expand_side(X->into(dir), T->t, &D->into(dir), &total, c->s_main, &e);
+    if (rc == 1)
+      PA_FAIL("exchange!(Table): the rows that part " + std::to_string(c->part) + " lists in " + side_name(1 - dir) +
+              " hold " + std::to_string(total) + " entries, more than Int32 ptrs address");
+    if (rc) PA_FAIL(std::string("exchange!(Table): deriving the exchanger failed: ") + hipGetErrorString(e));
+  }
+  D->max_lid = T->ndata - 1;
+  *out = D.get();
+  T->plans.emplace_back(X->id, std::move(D));
+  return 0;
+}
+
+// The checks and the derived exchangers of a table exchange; vs / vp: the
+// tables' data as the vectors of the exchange, dx: the derived exchangers.
+int table_exchange_setup(int n, pa_table* const tables[], pa_xchg* const xg[], int op, int dir,
+                         std::vector<pa_vec*>* vp, std::vector<pa_xchg*>* dx) {
+  CHECK_ARG(n >= 1 && tables && xg, "null argument");
+  CHECK_ARG(op == PA_REPLACE || op == PA_ADD, "invalid combine op");
+  for (int i = 0; i < n; ++i) {
+    CHECK_ARG(tables[i] && xg[i], "null handle");
+    CHECK_ARG(tables[i]->dtype == tables[0]->dtype, "exchange!(Table): element types differ across parts");
+    CHECK_ARG(tables[i]->ctx == xg[i]->ctx, "exchange!(Table): table and exchanger of different contexts");
+    CHECK_ARG(xg[i]->max_lid < tables[i]->nrows,
+              "exchange!(Table): the table has fewer rows than the exchanger's largest lid (BoundsError)");
+  }
+  vp->resize(n);
+  dx->resize(n);
+  for (int i = 0; i < n; ++i) {
+    (*vp)[i] = tables[i]->data;
+    if (table_plan(tables[i], xg[i], &(*dx)[i])) return -1;
+  }
+  // every edge between two parts of the call: equally many entries on both sides
+  for (int i = 0; i < n; ++i) {
+    const XchgSide& r = (*dx)[i]->into(dir);
+    const int me = xg[i]->ctx->part;
+    for (size_t k = 0; k < r.parts.size(); ++k) {
+      int j = -1;
+      for (int q = 0; q < n && j < 0; ++q)
+        if (xg[q]->ctx->part == r.parts[k]) j = q;
+      if (j < 0) continue;  // a part of another process: the caller's contract
+      const XchgSide& s = (*dx)[j]->from(dir);
+      const auto it = std::find(s.parts.begin(), s.parts.end(), me);
+      if (it == s.parts.end())
+        PA_FAIL("exchange!(Table): exchanger mismatch: part " + std::to_string(me) + " receives from part " +
+                std::to_string(r.parts[k]) + ", which does not send to it");
+      const size_t m = (size_t)(it - s.parts.begin());
+      const int64_t want = r.ptrs[k + 1] - r.ptrs[k], have = s.ptrs[m + 1] - s.ptrs[m];
+      if (want != have)
+        PA_FAIL("exchange!(Table): row lengths differ: part " + std::to_string(r.parts[k]) + " sends " +
+                std::to_string(have) + " entries to part " + std::to_string(me) + ", whose rows for them hold " +
+                std::to_string(want));
+    }
+  }
+  return exchange_check(n, vp->data(), dx->data(), op);
+}
+
+// the data of the rows the transfer left from become +0.0
+int table_zero_sent(pa_table* T, const pa_xchg* D, int dir, hipStream_t st) {
+  unsigned char z[16] = {0};
+  const XchgSide& sent = D->from(dir);
+  launch_fill(T->dtype, sent.n, 0, sent.lids, T->data->d, z, st);
+  return 0;
+}
+
+}  // namespace
+
+int pa_table_exchange_all(int n, pa_table* const tables[], pa_xchg* const xg[], int op, int reverse, int zero_sent) {
+  const int dir = reverse ? 1 : 0;
+  std::vector<pa_vec*> vp;
+  std::vector<pa_xchg*> dx;
+  if (table_exchange_setup(n, tables, xg, op, dir, &vp, &dx)) return -1;
+  TuneScope ts(tables[0]->ctx);
+  const int dt = tables[0]->dtype;
+  if (pre_pack_wait(n, dx.data())) return -1;
+  for (int i = 0; i < n; ++i)
+    if (exchange_pack(i, vp.data(), dx.data(), dir, dx[i]->ctx->s_main)) return -1;
+  HIPC(hipGetLastError());
+  bool pulled = false;  // no target vectors: staging copies (or RCCL), then the unpack kernels
+  if (transport(n, dx.data(), dt, dir, op, nullptr, &pulled)) return -1;
+  for (int i = 0; i < n; ++i) {
+    hipStream_t st = dx[i]->ctx->s_main;
+    if (exchange_unpack(i, vp.data(), dx.data(), nullptr, op, dir, pulled, 0, st)) return -1;
+    if (zero_sent && table_zero_sent(tables[i], dx[i], dir, st)) return -1;
+  }
+  HIPC(hipGetLastError());
+  return 0;
+}
+
+int pa_table_exchange_all_async(int n, pa_table* const tables[], pa_xchg* const xg[], int op, int reverse,
+                                int zero_sent, pa_event* const after[], pa_event* done[]) {
+  CHECK_ARG(done, "null done");
+  const int dir = reverse ? 1 : 0;
+  std::vector<pa_vec*> vp;
+  std::vector<pa_xchg*> dx;
+  if (table_exchange_setup(n, tables, xg, op, dir, &vp, &dx)) return -1;
+  TuneScope ts(tables[0]->ctx);
+  auto tail = [&](int i, hipStream_t st) -> int {
+    return zero_sent ? table_zero_sent(tables[i], dx[i], dir, st) : 0;
+  };
+  return exchange_async(n, vp.data(), dx.data(), nullptr, op, dir, 0, after, tail, done, /*pull=*/false);
 }
 
 // ---------------------------------------------------------------------------

@@ -591,6 +591,27 @@ struct pa_vec {
   pa::DevBuf<void> base;    // the allocation (null for views)
 };
 
+// One part's Table on the device (Helpers.jl:63-94): the row offsets and the
+// data as a vector, and the derived exchangers of the exchange!(Table) calls
+// it took part in (pa_table.hip), one per base exchanger id.  ptrs never
+// change after creation, so a derived exchanger stays valid for the table's
+// lifetime; it owns its lid lists, buffers and combine plans like any pa_xchg.
+struct pa_table {
+  pa_ctx* ctx = nullptr;
+  int dtype = PA_F64;
+  int64_t nrows = 0, ndata = 0;
+  pa::DevBuf<int32_t> t;     // nrows + 1 offsets, 0-based
+  pa_vec* data = nullptr;    // ndata values (pa_table_data hands out this view)
+  std::vector<std::pair<uint64_t, std::unique_ptr<pa_xchg>>> plans;
+};
+
+namespace pa {
+// pa_table.hip
+hipError_t table_ptrs(int64_t nrows, const int32_t* d_ptrs1, int32_t* t, int* bad, int64_t* ndata, hipStream_t st);
+int table_expand_side(const XchgSide& in, const int32_t* t, XchgSide* out, int64_t* total, hipStream_t st,
+                      hipError_t* err);
+}  // namespace pa
+
 // int32 words of a pattern slice's descriptor (dedup_patterns, SPMV_DESC):
 // 4 header words + the slice's H/64 64-bit mask words, a power of two
 constexpr int desc_words(int R) { return R <= 2 ? 8 : 16; }

@@ -425,6 +425,89 @@ class DeviceVector:
             pass
 
 
+class _TableData(DeviceVector):
+    """the pa_vec view of a table's data (pa_table_data): the table owns it"""
+
+    def __init__(self, table, h, dtype, n):
+        self.ctx, self.dtype, self.n, self.h, self.table = table.ctx, np.dtype(dtype), int(n), h, table
+
+    def __del__(self):
+        pass
+
+
+# integer payloads travel as the bit patterns of the float type of their width
+_TABLE_CARRIER = {np.dtype(np.int32): np.dtype(np.float32), np.dtype(np.int64): np.dtype(np.float64)}
+
+
+class DeviceTable:
+    """pa_table: one part's Table (Helpers.jl:63-94) in HBM, rows of any
+    length.  `dtype` is the payload type: one of the four element types, or
+    int32 / int64 (ids), which the device carries as the bits of Float32 /
+    Float64 (exchange with replace only).  `ptrs`: the nrows + 1 1-based Int32
+    row pointers, a host array or a DeviceArray of int32 on the part's device.
+    `data` is the payload as a DeviceVector of the carrier type."""
+
+    def __init__(self, ctx: PartContext, dtype, ptrs):
+        self.ctx = ctx
+        self.dtype = np.dtype(dtype)
+        self.carrier = _TABLE_CARRIER.get(self.dtype, self.dtype)
+        if self.carrier not in _lib.DTYPES:
+            raise TypeError(f"DeviceTable: no device element type for {self.dtype}")
+        if isinstance(ptrs, DeviceArray):
+            if ptrs.dtype != np.dtype(np.int32) or ptrs.n < 1:
+                raise TypeError("DeviceTable: device ptrs must be an Int32 DeviceArray of nrows + 1 entries")
+            nrows, pp, on_device = ptrs.n - 1, C.c_void_p(ptrs.ptr), 1
+        else:
+            keep, _ = _lib.i32(ptrs)
+            if keep.ndim != 1 or len(keep) < 1:
+                raise ValueError("DeviceTable: ptrs must hold nrows + 1 entries")
+            nrows, pp, on_device = len(keep) - 1, keep.ctypes.data_as(C.c_void_p), 0
+        h = C.c_void_p()
+        _lib.call("pa_table_create", ctx.h, _lib.DTYPES[self.carrier], nrows, pp, on_device, C.byref(h))
+        self.h = h
+        a, b = C.c_int64(), C.c_int64()
+        _lib.call("pa_table_info", h, C.byref(a), C.byref(b))
+        self.nrows, self.ndata = a.value, b.value
+        v = C.c_void_p()
+        _lib.call("pa_table_data", h, C.byref(v))
+        self.data = _TableData(self, v, self.carrier, self.ndata)
+
+    @staticmethod
+    def from_host(ctx: PartContext, table, dtype=None) -> "DeviceTable":
+        """the device copy of a host Table; dtype: the payload type (default: the data's)"""
+        t = DeviceTable(ctx, dtype if dtype is not None else np.asarray(table.data).dtype, table.ptrs)
+        t.upload(table.data)
+        return t
+
+    def upload(self, data):
+        a = np.ascontiguousarray(data, dtype=self.dtype)
+        if a.shape != (self.ndata,):
+            raise ValueError(f"DeviceTable.upload: expected {self.ndata} entries, got {a.shape}")
+        self.data.upload(a.view(self.carrier))
+
+    def download(self):
+        """the data as a host array of the payload type"""
+        return self.data.download().view(self.dtype)
+
+    def ptrs(self):
+        """the 1-based Int32 row pointers, read back from the device (pa_table_ptrs)"""
+        p = np.empty(self.nrows + 1, dtype=np.int32)
+        _lib.call("pa_table_ptrs", self.h, p.ctypes.data_as(C.POINTER(C.c_int32)))
+        return p
+
+    def to_host(self):
+        """Table(data, ptrs) of the payload type"""
+        from .helpers import Table
+        return Table(self.download(), self.ptrs())
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None) and _lib._lib is not None and not sys.is_finalizing():
+                _lib._lib.pa_table_destroy(self.h)
+        except Exception:
+            pass
+
+
 class DeviceArray:
     """A device array the caller owns, passed to the library by address
     (on_device = 1 of pa_vec_scatter / pa_vec_gather): `n` values of `dtype`

@@ -18,8 +18,8 @@ import numpy as np
 from . import _lib
 from .backends import MAIN, PData, exchange, get_part_ids, map_parts, unzip
 from .backends import gather as _gather_pdata
-from .device import (DeviceArray, DeviceCOO, DeviceIndex, DeviceMatrix, DeviceMatrixExchanger, DeviceVector, Task,
-                     contexts, device_exchanger, device_index, device_index_gids)
+from .device import (DeviceArray, DeviceCOO, DeviceIndex, DeviceMatrix, DeviceMatrixExchanger, DeviceTable,
+                     DeviceVector, Task, contexts, device_exchanger, device_index, device_index_gids)
 from .helpers import Table, counts_to_ptrs, trace_setup
 from .prange import (Exchanger, PRange, _cached_eq, add_gids_, empty_exchanger, hids_are_equal, lids_are_equal,
                      oids_are_equal, prange_linear, to_main)
@@ -660,6 +660,48 @@ def async_assemble_(v, t0: PData = None, rows: PRange = None) -> PData:
     """t = async_assemble!(v) (Interfaces.jl:2084-2106; a PSparseMatrix:
     2383-2404): assemble_ as async_exchange_ runs exchange_."""
     return _async(v, rows, t0, "pa_coo_assemble_all", _lib.PA_ADD, 1, 1)
+
+
+def _table_args(values: PData, exchanger, combine, reverse, zero_sent):
+    """the arguments pa_table_exchange_all and its async twin share"""
+    if combine not in (None, "+"):
+        raise ValueError("exchange!(Table): combine is None (replace) or '+'")
+    tabs = values.parts
+    if not all(isinstance(t, DeviceTable) for t in tabs):
+        raise TypeError("exchange!(Table): values must be a PData of DeviceTable (DeviceTable.from_host)")
+    if combine == "+" and any(t.dtype.kind in "iu" for t in tabs):
+        raise TypeError("exchange!(+, Table): integer tables travel as bit patterns and cannot be added")
+    ctxs = contexts(values)
+    xg = [device_exchanger(c, exchanger, p) for c, p in zip(ctxs, values.part_ids)]
+    op = _lib.PA_ADD if combine == "+" else _lib.PA_REPLACE
+    return ctxs, (len(ctxs), _hs(tabs), _hs(xg), op, 1 if reverse else 0, 1 if zero_sent else 0)
+
+
+def exchange_table_(values: PData, exchanger, combine=None, reverse=False, zero_sent=False) -> PData:
+    """exchange!([combine_op,] values::AbstractPData{<:Table}, exchanger)
+    (Interfaces.jl:891-961) over DeviceTables, rows of any length per lid: the
+    exchanger derived from `exchanger` and each table's ptrs is built on the
+    device on a table's first call and kept on the table.  combine None
+    replaces, "+" adds (contributions in the reference's order); reverse uses
+    reverse(exchanger); zero_sent zeroes the data of the rows that were sent
+    afterwards.  A sender's row and its receiver's row must be equally long."""
+    _, args = _table_args(values, exchanger, combine, reverse, zero_sent)
+    _lib.call("pa_table_exchange_all", *args)
+    return values
+
+
+def async_exchange_table_(values: PData, exchanger, combine=None, reverse=False, zero_sent=False,
+                          t0: PData = None) -> PData:
+    """t = async_exchange!([combine_op,] values::AbstractPData{<:Table},
+    exchanger, t0): exchange_table_ on the parts' comm streams, a PData of
+    Tasks as async_exchange_ returns."""
+    ctxs, args = _table_args(values, exchanger, combine, reverse, zero_sent)
+    if t0 is not None and t0.part_ids != values.part_ids:
+        raise ValueError("t0: tasks over different parts")
+    after = _hs(t0.parts) if t0 is not None else None
+    done = (C.c_void_p * len(ctxs))()
+    _lib.call("pa_table_exchange_all_async", *args, after, done)
+    return _tasks(values, ctxs, [C.c_void_p(h) for h in done])
 
 
 def wait_all(tasks: PData):
