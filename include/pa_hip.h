@@ -726,6 +726,56 @@ int pa_cg_update_all(int n, pa_vec* const x[], pa_vec* const r[],
                      const pa_index* const idx[], const void* alpha,
                      double* rnorm);
 
+/* ---- Jacobi-preconditioned CG ---------------------------
+ * IterativeSolvers.cg!(x, A, b; Pl = Diagonal(diag(A))) over device
+ * operations.  Float32 and Float64 only: with a complex element type all
+ * three entries fail with a message before anything is touched (the scalar
+ * recurrence's Complex/Complex divisions are not pinned by anything here).
+ *
+ * pa_mat_diag: d (num_lids(cols) elements of A's dtype) is set to zero(T)
+ * everywhere, then for every owned row with a stored entry in its own column
+ * d[col lid of that id] takes the stored value — diag(A) of the part's
+ * owned block.  rows and cols are the matrix's index sets and must own the
+ * same ids in the same order.  Stored ghost rows are skipped, an absent
+ * diagonal stays +0.0, ghost lids stay +0.0 (the caller exchanges d).  The
+ * (row, col) of a value is derived from what the matrix keeps for mul! —
+ * the slice offsets and int32 columns of the SELL slots, the Float32
+ * delta16 interleave of 4 rows per lane, the long rows' CSR, the columns'
+ * oid_to_lid — one thread per owned row, plain stores (each row has at most
+ * one such entry).  The entry table is neither used nor built
+ * (pa_mat_entry_info is unchanged), nothing is copied to the host, and the
+ * work is stream-ordered on the part's compute stream.  It reads the values
+ * the owner stores, so for an FE matrix it belongs after assemble!(A).  A
+ * matrix that does not keep that layout fails with a message, as
+ * pa_mat_set_values does for one without a nonzero map (pa_mat_stencil
+ * matrices keep the slots and their columns, so they have a diagonal here).
+ *
+ * pa_pcg_apply_all: c[i] = r[i] / d[i] over all lids — one IEEE division in
+ * T per element, no reciprocal, what ldiv!(c, Diagonal(d), r) computes — and
+ * *rho = dot(c, r) over the owned lids, accumulated in the same pass (rho: a
+ * host scalar of the element type).  A zero in d gives Inf / NaN, as in
+ * Julia.  c may be r.
+ *
+ * pa_pcg_update_all: the tail of one preconditioned iteration and the head
+ * of the next in one pass over all lids: x .+= α.*u; r .-= α.*c;
+ * c = r_new ./ d, and over the owned lids *rnorm = norm(r_new) and
+ * *rho = dot(c_new, r_new).  alpha is a host scalar OF THE ELEMENT TYPE (the
+ * preconditioned recurrence's α = ρ/dot(u, c) is a T, unlike
+ * pa_cg_update_all's Float64 α): each element is evaluated in T, rounded at
+ * every operation, no FMA.  The five vectors share one partition whose
+ * owned lids are contiguous (0..noids-1: the reductions ride in the element
+ * pass; anything else is an error, the caller checks).
+ *
+ * Reductions as the others': a Float64 accumulator, per-block partials
+ * folded in block order, each part's value rounded to T, the parts added in
+ * part order in T; norm's ^(1/2) is Float64.  pa_pcg_apply_all serves any
+ * layout (ldiv! has no layout condition): with contiguous owned lids its dot
+ * rides in the element pass, otherwise it runs as a reduction of its own
+ * through oid_to_lid, same result.                                        */
+int pa_mat_diag(const pa_mat* A, const pa_index* rows, const pa_index* cols, pa_vec* d);
+int pa_pcg_apply_all(int n, pa_vec* const c[], const pa_vec* const r[], const pa_vec* const d[], const pa_index* const idx[], void* rho);
+int pa_pcg_update_all(int n, pa_vec* const x[], pa_vec* const r[], const pa_vec* const u[], pa_vec* const c[], const pa_vec* const d[], const pa_index* const idx[], const void* alpha, double* rnorm, void* rho);
+
 /* IterativeSolvers.cg!(x, A, b; reltol, abstol, maxiter) (v0.9, not
  * vendored; called at test_fdm.jl:115, test_fem_sa.jl:135, recurrence in
  * SURVEY.md §3.5) with the scalar recurrence on the device (SURVEY.md §8f

@@ -1450,11 +1450,57 @@ function _host_broadcasted(bc::HIPBroadcasted)
   end
 end
 
+# ---- Jacobi preconditioner (DESIGN.md §4.11) --------------------------------
+# diag(A) read off the device layout (pa_mat_diag: no entry table, no nzval
+# download), ghosts exchanged from their owners, and P = HIPJacobi(A) with
+# ldiv!(c, P, r) on the device, so IterativeSolvers.cg!(x, A, b; Pl=P) — the
+# generic iterate, see below — runs on device operations.  Float32 / Float64.
+const PcgEltype = Union{Float32,Float64}
+function LinearAlgebra.diag(A::HIPMatrix{T}) where {T<:PcgEltype}
+  oids_are_equal(A.rows, A.cols) || error("diag: A.rows and A.cols own different ids")
+  d = PVector{T}(undef, A.cols)
+  M = dev_mat(A); R = dev_idx(A.rows); K = dev_idx(A.cols); D = dev_vec_nocopy(d)
+  for i in eachindex(M)
+    check(ccall((:pa_mat_diag, libpa), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                M[i], R[i], K[i], D[i]))
+  end
+  mark_device_newer!(d)
+  PartitionedArrays.exchange!(d)
+  d
+end
+struct HIPJacobi{V}
+  d::V   # the diagonal on every lid (a HIPVector on the solve's PRange)
+end
+HIPJacobi(A::PSparseMatrix) = HIPJacobi(diag(A))
+function LinearAlgebra.ldiv!(c::HIPVector{T}, P::HIPJacobi, r::HIPVector{T}) where {T<:PcgEltype}
+  (c.rows === r.rows && r.rows === P.d.rows) || error("ldiv!(c, ::HIPJacobi, r): one PRange for c, r and the diagonal")
+  rho = Ref{T}(zero(T))
+  check(ccall((:pa_pcg_apply_all, libpa), Cint,
+              (Cint, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ref{T}),
+              num_parts(c.values), dev_vec_nocopy(c), dev_vec(r), dev_vec(P.d), dev_idx(c.rows), rho))
+  mark_device_newer!(c)
+  c
+end
+# x .+= α.*u; r .-= α.*c; c = P \ r in one pass: (norm(r), dot(c, r)) of the new values
+function pcg_update!(x::HIPVector{T}, r::HIPVector{T}, u::HIPVector{T}, c::HIPVector{T}, P::HIPJacobi,
+                     α::Number) where {T<:PcgEltype}
+  a = Ref{T}(T(α)); rho = Ref{T}(zero(T)); res = Ref{Float64}(0.0)
+  check(ccall((:pa_pcg_update_all, libpa), Cint,
+              (Cint, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}},
+               Ptr{Ptr{Cvoid}}, Ref{T}, Ref{Float64}, Ref{T}),
+              num_parts(x.values), dev_vec(x), dev_vec(r), dev_vec(u), dev_vec(c), dev_vec(P.d),
+              dev_idx(x.rows), a, res, rho))
+  mark_device_newer!(x); mark_device_newer!(r); mark_device_newer!(c)
+  res[], rho[]
+end
+
 # ---- IterativeSolvers.cg! (v0.9) with the recurrence on the device --------
 # (pa_cg_solve_all: the same iterates as the generic cg! over the
 # specialisations above, bit for bit, with no host round trip per iteration)
 # log = true returns IterativeSolvers' ConvergenceHistory: that keeps the
 # generic cg! (over the specialisations above); verbose is not printed here.
+# Pl = HIPJacobi(A) keeps the generic cg! too: its ldiv!(c, Pl, r), dot, mul!
+# and broadcasts are the device operations above.
 function IterativeSolvers.cg!(x::HIPVector{T}, A::HIPMatrix{T}, b::HIPVector{T};
                               abstol::Real=zero(real(T)), reltol::Real=sqrt(eps(real(T))),
                               maxiter::Int=size(A, 2), log::Bool=false, initially_zero::Bool=false,

@@ -133,6 +133,10 @@ _SIGS = {
     "pa_spmv_all": [C.c_int, C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), _p, _p],
     "pa_spmv_dot_all": [C.c_int, C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), _p, _p, _p],
     "pa_cg_update_all": [C.c_int, C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), _p, C.POINTER(C.c_double)],
+    "pa_mat_diag": [_p, _p, _p, _p],
+    "pa_pcg_apply_all": [C.c_int, C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), _p],
+    "pa_pcg_update_all": [C.c_int, C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.POINTER(_p),
+                          C.POINTER(_p), _p, C.POINTER(C.c_double), _p],
     "pa_cg_solve_all": [C.c_int, C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.POINTER(_p),
                         C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.c_double, C.c_double, C.c_int64, C.c_int,
                         _i64p, C.POINTER(C.c_double), C.POINTER(C.c_double)],

@@ -154,6 +154,12 @@ void launch_u_fill(const pa_mat* A, hipStream_t st);
 void launch_t_gbase(const pa_mat* A, int64_t noids, int32_t* ok, hipStream_t st);
 void launch_t_fill(const pa_mat* A, int64_t noids, bool codes, hipStream_t st);
 void launch_t_check(const pa_mat* A, unsigned* bad, hipStream_t st);
+// Jacobi-preconditioned CG (pa_pcg.hip)
+void launch_mat_diag(const pa_mat* A, const int32_t* own, void* d, int64_t nd, hipStream_t st);
+void launch_pcg_apply(int dtype, int64_t n, int64_t noids, void* c, const void* r, const void* d, double* part,
+                      int nb, hipStream_t st);
+void launch_pcg_update(int dtype, int64_t n, int64_t noids, void* x, void* r, const void* u, void* c, const void* d,
+                       const void* alpha, void* part, int nb, hipStream_t st);
 
 }  // namespace pa
 
@@ -4706,6 +4712,127 @@ int pa_cg_update_all(int n, pa_vec* const x[], pa_vec* const r[], const pa_vec* 
   std::vector<c128> vals;
   if (gather_results(n, ctxs.data(), false, &vals)) return -1;
   *rnorm = std::sqrt(fold_parts(dt, vals, true).re);  // (…)^(1/2) in Float64, correctly rounded
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Jacobi-preconditioned CG (kernels in pa_pcg.hip).  Real
+// element types: ρ/ρ_prev and ρ/dot of a complex recurrence would need
+// Julia's Complex/Complex division restated, and nothing pins it.
+
+static bool real_dtype(int dt) { return dt == PA_F32 || dt == PA_F64; }
+
+int pa_mat_diag(const pa_mat* A, const pa_index* rows, const pa_index* cols, pa_vec* d) {
+  const std::string w = "pa_mat_diag: ";
+  CHECK_ARG(A && rows && cols && d, w + "null argument");
+  CHECK_ARG(real_dtype(A->dtype), w + "complex element types are not supported (Float32 and Float64 only)");
+  CHECK_ARG(d->dtype == A->dtype, w + "d must have the matrix's element type");
+  CHECK_ARG(A->ctx == rows->ctx && A->ctx == cols->ctx && A->ctx == d->ctx,
+            w + "the matrix, the index sets and d belong to different parts");
+  CHECK_ARG(rows->noids == A->main.nrows && cols->nlids == A->ncols_lids,
+            w + "the index sets do not have the matrix's local ids");
+  CHECK_ARG(cols->noids == rows->noids, w + "rows and cols must own the same ids");
+  CHECK_ARG(d->n == cols->nlids, w + "d must have num_lids(cols) elements");
+  // the SELL slots with their int32 columns and the long rows' CSR: what
+  // every builder of this library leaves behind
+  CHECK_ARG(A->main.slots == 0 || (A->main.off.p && A->main.col.p && A->main.val.p),
+            w + "matrix does not keep the SELL layout with int32 columns");
+  CHECK_ARG(A->n_long == 0 || (A->d_long_row.p && A->d_long_ptr.p && A->d_long_col.p),
+            w + "matrix does not keep its long rows' CSR");
+  pa_ctx* c = A->ctx;
+  HIPC(hipSetDevice(c->device));
+  if (d->n > 0) HIPC(hipMemsetAsync(d->d, 0, (size_t)d->n * dtype_size(d->dtype), c->s_main));  // zero(T): +0.0
+  launch_mat_diag(A, cols->own_contig ? nullptr : cols->d_oid_to_lid.p, d->d, d->n, c->s_main);
+  HIPC(hipGetLastError());
+  return 0;
+}
+
+// the checks the two fused PCG entries share: v[k][i], k < nv, are the
+// vectors of part i (all of one partition and element type)
+static int pcg_check(const std::string& w, int n, int nv, const pa_vec* const* const v[],
+                     const pa_index* const idx[]) {
+  CHECK_ARG(n >= 1 && idx, w + "null argument");
+  for (int k = 0; k < nv; ++k) CHECK_ARG(v[k], w + "null argument");
+  for (int i = 0; i < n; ++i) {
+    CHECK_ARG(idx[i], w + "null handle");
+    for (int k = 0; k < nv; ++k) CHECK_ARG(v[k][i], w + "null handle");
+  }
+  const int dt = v[0][0]->dtype;
+  CHECK_ARG(real_dtype(dt), w + "complex element types are not supported (Float32 and Float64 only)");
+  for (int i = 0; i < n; ++i) {
+    const int64_t m = v[0][i]->n;
+    CHECK_ARG(idx[i]->nlids == m, w + "vectors must share the partition");
+    for (int k = 0; k < nv; ++k) {
+      CHECK_ARG(v[k][i]->n == m, w + "vectors must share the partition");
+      CHECK_ARG(v[k][i]->dtype == dt, w + "element types differ");
+      CHECK_ARG(v[k][i]->ctx == v[0][i]->ctx, w + "vectors of one part belong to different contexts");
+    }
+  }
+  return 0;
+}
+
+static inline int pcg_blocks(int64_t m) { return (int)std::min<int64_t>(8192, std::max<int64_t>(1, (m + 255) / 256)); }
+
+int pa_pcg_apply_all(int n, pa_vec* const c[], const pa_vec* const r[], const pa_vec* const d[],
+                     const pa_index* const idx[], void* rho) {
+  const std::string w = "pa_pcg_apply_all: ";
+  CHECK_ARG(rho, w + "null argument");
+  const pa_vec* const* const v[3] = {c, r, d};
+  if (pcg_check(w, n, 3, v, idx)) return -1;
+  const int dt = c[0]->dtype;
+  std::vector<pa_ctx*> ctxs(n);
+  for (int i = 0; i < n; ++i) {
+    pa_ctx* cx = c[i]->ctx;
+    ctxs[i] = cx;
+    HIPC(hipSetDevice(cx->device));
+    const int64_t m = c[i]->n;
+    const int nb = pcg_blocks(m);
+    if (idx[i]->own_contig) {
+      launch_pcg_apply(dt, m, idx[i]->noids, c[i]->d, r[i]->d, d[i]->d, (double*)cx->d_partials, nb, cx->s_main);
+      launch_fold(0, nb, cx->d_partials, cx->d_fold, cx->d_result, cx->d_ticket, cx->s_main);
+    } else {  // unfused: the division, then the dot reduction through the owned lids
+      launch_pcg_apply(dt, m, 0, c[i]->d, r[i]->d, d[i]->d, (double*)cx->d_partials, nb, cx->s_main);
+      launch_reduce(dt, 0, idx[i]->noids, idx[i]->d_oid_to_lid, c[i]->d, idx[i]->d_oid_to_lid, r[i]->d,
+                    cx->d_partials, cx->d_result, cx->d_ticket, cx->s_main);
+    }
+  }
+  HIPC(hipGetLastError());
+  std::vector<c128> vals;
+  if (gather_results(n, ctxs.data(), false, &vals)) return -1;
+  store_scalar(dt, fold_parts(dt, vals, false), rho);
+  return 0;
+}
+
+int pa_pcg_update_all(int n, pa_vec* const x[], pa_vec* const r[], const pa_vec* const u[], pa_vec* const c[],
+                      const pa_vec* const d[], const pa_index* const idx[], const void* alpha, double* rnorm,
+                      void* rho) {
+  const std::string w = "pa_pcg_update_all: ";
+  CHECK_ARG(alpha && rnorm && rho, w + "null argument");
+  const pa_vec* const* const v[5] = {x, r, u, c, d};
+  if (pcg_check(w, n, 5, v, idx)) return -1;
+  const int dt = x[0]->dtype;
+  // the reductions ride in the element pass over lids 0..noids-1: the caller
+  // checks the layout (pamd.cg_ composes the separate operations otherwise)
+  for (int i = 0; i < n; ++i)
+    CHECK_ARG(idx[i]->own_contig, w + "the owned lids must be contiguous (0..noids-1)");
+  std::vector<pa_ctx*> ctxs(n);
+  for (int i = 0; i < n; ++i) {
+    pa_ctx* cx = x[i]->ctx;
+    ctxs[i] = cx;
+    HIPC(hipSetDevice(cx->device));
+    const int64_t m = x[i]->n;
+    const int nb = pcg_blocks(m);
+    launch_pcg_update(dt, m, idx[i]->noids, x[i]->d, r[i]->d, u[i]->d, c[i]->d, d[i]->d, alpha, cx->d_partials, nb,
+                      cx->s_main);
+    // {Σ r², Σ c*r} per part: one c128 accumulator, folded componentwise
+    launch_fold(1, nb, cx->d_partials, cx->d_fold, cx->d_result, cx->d_ticket, cx->s_main);
+  }
+  HIPC(hipGetLastError());
+  std::vector<c128> vals;
+  if (gather_results(n, ctxs.data(), true, &vals)) return -1;
+  *rnorm = std::sqrt(fold_parts(dt, vals, true).re);  // (…)^(1/2) in Float64, correctly rounded
+  for (auto& p : vals) p.re = p.im;
+  store_scalar(dt, fold_parts(dt, vals, true), rho);
   return 0;
 }
 

@@ -1427,7 +1427,7 @@ def _own_contig(v: PVector) -> bool:
 
 
 def cg_(x: PVector, A: PSparseMatrix, b: PVector, reltol=None, abstol=0.0, maxiter=None,
-        history=None, fused=True, device=False, batch=8):
+        history=None, fused=True, device=False, batch=8, Pl=None):
     """IterativeSolvers.cg! (v0.9; caller of the hot path at test_fdm.jl:115,
     test_fem_sa.jl:135), restated over the device operations:
     u = zero(x); r, c = similar(x); copyto!(r, b); mul!(c, A, x); r .-= c;
@@ -1437,12 +1437,19 @@ def cg_(x: PVector, A: PSparseMatrix, b: PVector, reltol=None, abstol=0.0, maxit
 
     device=True runs the same recurrence with its scalars on the device
     (pa_cg_solve_all): the host enqueues `batch` iterations between reads of
-    the done flag; results equal the host-driven fused loop bit for bit."""
+    the done flag; results equal the host-driven fused loop bit for bit.
+
+    Pl: a left preconditioner (Jacobi); the preconditioned iterate then runs
+    (_pcg), host-driven, Float32 / Float64.  Pl=None is the loop above."""
     real = np.float32 if x.dtype in (np.float32, np.complex64) else np.float64
     if reltol is None:  # sqrt(eps(real(eltype(b)))), in that type
         reltol = float(np.sqrt(np.finfo(real).eps))
     if maxiter is None:
         maxiter = len(A.cols)
+    if Pl is not None:
+        if device:
+            raise NotImplementedError("cg_(Pl=..., device=True): the preconditioned recurrence is host-driven")
+        return _pcg(x, A, b, Pl, reltol, abstol, maxiter, history, fused)
     if device:
         return _cg_device(x, A, b, reltol, abstol, maxiter, history, batch)
     u = x.similar().fill_(0)
@@ -1502,6 +1509,137 @@ def _cg_device(x: PVector, A: PSparseMatrix, b: PVector, reltol, abstol, maxiter
               hist.ctypes.data_as(C.POINTER(C.c_double)) if hist is not None else None)
     if history is not None:
         history.extend(float(v) for v in hist[:its.value])
+    return x
+
+
+# ---------------------------------------------------------------------------
+# Jacobi-preconditioned CG: diag(A) read off the device
+# layout, Pl \ r fused with ρ = dot(c, r), and the x / r updates fused with
+# the next iteration's Pl \ r, norm(r) and ρ.
+
+def _real_only(dtype, what):
+    if np.dtype(dtype).kind == "c":
+        raise NotImplementedError(f"{what}: complex element types are not supported (Float32 and Float64 only)")
+
+
+def diag(A: PSparseMatrix) -> PVector:
+    """diag(A) as a PVector on A.cols (pa_mat_diag): the stored diagonal entry
+    of every owned row (+0.0 where the pattern has none), then exchange! once,
+    so every ghost value equals its owner's and a division over all lids never
+    divides by a ghost slot's zero.  It reads the entry the owner stores: for
+    a matrix assembled from cell contributions it belongs after assemble_(A).
+    The entry table is not built and nzval is not downloaded."""
+    _real_only(A.dtype, "diag")
+    if not oids_are_equal(A.rows, A.cols):
+        raise AssertionError("diag: A.rows and A.cols own different ids")
+    d = PVector.undef(A.cols, A.dtype)
+    for M, (r, c), dv in zip(A.values.parts, _mat_index(A, False), d.values.parts):
+        _lib.call("pa_mat_diag", M.h, r.h, c.h, dv.h)
+    return exchange_(d)
+
+
+class Jacobi:
+    """The diagonal preconditioner Diagonal(diag(A)): Jacobi(A), or Jacobi(d)
+    from a PVector holding the diagonal on every lid.  A zero diagonal is no
+    error: it yields Inf / NaN, as ldiv!(c, Diagonal(d), r) does in Julia."""
+
+    def __init__(self, A_or_d):
+        self.d = diag(A_or_d) if isinstance(A_or_d, PSparseMatrix) else A_or_d
+        if not isinstance(self.d, PVector):
+            raise TypeError("Jacobi: a PSparseMatrix or a PVector")
+        _real_only(self.d.dtype, "Jacobi")
+
+
+def _on_rows(d: PVector, like: PVector) -> PVector:
+    """d as a vector of like's PRange object (owned values copied, ghosts exchanged)"""
+    if d.rows is like.rows:
+        return d
+    dd = like.similar(dtype=d.dtype)
+    copyto_(dd, d)
+    return exchange_(dd)
+
+
+def pcg_apply_(c: PVector, r: PVector, d: PVector):
+    """c .= r ./ d over all lids and dot(c, r) in one pass (pa_pcg_apply_all);
+    the three vectors share one PRange.  Returns the dot, of the element type."""
+    if not (c.rows is r.rows is d.rows):
+        raise ValueError("pcg_apply_: the three vectors must share one PRange")
+    out = _scalar_out(c.dtype)
+    _lib.call("pa_pcg_apply_all", len(c.values.parts), _hs(c.values.parts), _hs(r.values.parts), _hs(d.values.parts),
+              _lib.ptr_array(_idx(c)), out.ctypes.data_as(C.c_void_p))
+    return out[0]
+
+
+def pcg_update_(x: PVector, r: PVector, u: PVector, c: PVector, d: PVector, alpha):
+    """x .+= α.*u; r .-= α.*c; c .= r ./ d in one pass over all lids
+    (pa_pcg_update_all), α converted to the element type.  Returns norm(r)
+    (a float) and dot(c, r) (of the element type) of the new values.  The
+    owned lids must be contiguous (the entry refuses anything else)."""
+    if not (x.rows is r.rows is u.rows is c.rows is d.rows):
+        raise ValueError("pcg_update_: the five vectors must share one PRange")
+    al, alp = _lib.scalar_buf(alpha, x.dtype)
+    nr = C.c_double(0.0)
+    out = _scalar_out(x.dtype)
+    _lib.call("pa_pcg_update_all", len(x.values.parts), _hs(x.values.parts), _hs(r.values.parts),
+              _hs(u.values.parts), _hs(c.values.parts), _hs(d.values.parts), _lib.ptr_array(_idx(x)), alp,
+              C.byref(nr), out.ctypes.data_as(C.c_void_p))
+    return nr.value, out[0]
+
+
+def _pcg(x: PVector, A: PSparseMatrix, b: PVector, Pl, reltol, abstol, maxiter, history, fused):
+    """IterativeSolvers 0.9's preconditioned CG iterate with Pl = Jacobi:
+    u = 0; r = b - A*x; residual = norm(r); ρ = one(T); per iteration
+    c = Pl \\ r; ρ_prev = ρ; ρ = dot(c, r); β = ρ/ρ_prev; u .= c .+ β.*u;
+    c = A*u; α = ρ/dot(u, c); x .+= α.*u; r .-= α.*c; residual = norm(r).
+    ρ, β and α are of the element type T (dot of two PVectors is a T), the
+    residual a Float64.  fused: Pl \\ r with ρ once (pa_pcg_apply_all), then
+    per iteration the u update, mul! with dot(u, c), and the x / r updates
+    with the next Pl \\ r, norm(r) and ρ in one pass (pa_pcg_update_all);
+    otherwise the same arithmetic from the separate operations.  The fused
+    pass and mul!'s fused dot need contiguous owned lids: this is the caller's
+    check the entries ask for, and other layouts take the separate operations."""
+    if not isinstance(Pl, Jacobi):
+        raise TypeError("cg_(Pl=...): Pl must be a Jacobi")
+    _real_only(x.dtype, "cg_(Pl=...)")
+    T = np.dtype(x.dtype).type
+    if Pl.d.dtype != x.dtype:
+        raise TypeError("cg_(Pl=...): the preconditioner's element type differs from x's")
+    u = x.similar().fill_(0)
+    r = x.similar()
+    c = x.similar()
+    d = _on_rows(Pl.d, x)
+    copyto_(r, b)
+    mul_(c, A, x)
+    sub_(r, c)
+    residual = norm(r)
+    tol = max(reltol * norm(b), abstol)
+    rho = T(1)
+    it = 0
+    fuse = fused and _own_contig(u)
+    done = lambda: it >= maxiter or residual <= tol
+    if fuse and not done():
+        rho_next = pcg_apply_(c, r, d)
+    with np.errstate(all="ignore"):  # a zero ρ or dot gives Inf / NaN as in Julia
+        while not done():
+            if fuse:
+                rho_prev, rho = rho, T(rho_next)
+            else:
+                assign_(c, r / d)
+                rho_prev, rho = rho, T(dot(c, r))
+            beta = T(rho / rho_prev)
+            xpby_(u, c, beta)
+            if fuse:
+                alpha = T(rho / T(mul_dot_(c, A, u)))
+                residual, rho_next = pcg_update_(x, r, u, c, d, alpha)
+            else:
+                mul_(c, A, u)
+                alpha = T(rho / T(dot(u, c)))
+                axpy_(x, alpha, u)
+                axmy_(r, alpha, c)
+                residual = norm(r)
+            it += 1
+            if history is not None:
+                history.append(residual)
     return x
 
 
@@ -1700,7 +1838,16 @@ def lu_(F: PLU, A: PSparseMatrix) -> PLU:
 
 def ldiv_(c: PVector, F: PLU, b: PVector) -> PVector:
     """ldiv!(c, F, b) (Interfaces.jl:2656-2662): b gathered through F.rows,
-    solved on MAIN's host, and scattered into c's owned values."""
+    solved on MAIN's host, and scattered into c's owned values.
+
+    ldiv!(c, P::Jacobi, b): c .= b ./ P.d over all lids on the device
+    (pa_pcg_apply_all; its dot is discarded)."""
+    if isinstance(F, Jacobi):
+        _real_only(c.dtype, "ldiv_(c, Jacobi, b)")
+        if c.rows is not b.rows:
+            raise ValueError("ldiv_(c, Jacobi, b): c and b must share one PRange")
+        pcg_apply_(c, b, _on_rows(F.d, c))
+        return c
     b_in_main = gather(b, F.rows)
     c_in_main = PVector.full(0, F.cols, dtype=c.dtype)
     _main_maps(c.rows, F.cols)
