@@ -796,6 +796,35 @@ int pa_cg_solve_all(int n, pa_mat* const A[], pa_vec* const x[],
                     double reltol, double abstol, int64_t maxiter, int batch,
                     int64_t* iterations, double* residual, double* history);
 
+/* IterativeSolvers.cg!(x, A, b; Pl = Diagonal(d), reltol, abstol, maxiter)
+ * (v0.9) with the scalar recurrence on the device: the
+ * arguments and checks of pa_cg_solve_all, plus d, the diagonal on every lid
+ * of the solve's range (pa_mat_diag followed by an exchange).  Float32 and
+ * Float64 only.  Setup as cg_iterator!: u = 0, r = b - A*x, residual =
+ * norm(r), tolerance = max(reltol*norm(b), abstol), ρ = one(T); unless the
+ * solve is already done, c = r ./ d and ρ = dot(c, r) (pa_pcg_apply_all's
+ * kernel).  Then per iteration β = ρ/ρ_prev, u .= c .+ β.*u, mul!(c, A, u)
+ * with dot(u, c) fused, α = ρ/dot, x .+= α.*u, r .-= α.*c, c = r ./ d,
+ * residual = norm(r), ρ_prev = ρ, ρ = dot(c, r) — ρ, β and α of the element
+ * type, every operation rounded in it, the residual a Float64: the
+ * arithmetic of the host-driven loop over pa_vec_axpby, pa_spmv_dot_all and
+ * pa_pcg_update_all, bit for bit (x, history, iteration count).  The host
+ * enqueues `batch` iterations between reads of the first part's done flag;
+ * in the iterations of a batch that follow convergence (at most batch-1) the
+ * kernels that write x, r, u and the state return at once, but mul!(c, A, u),
+ * its dot and the gathers still run, so the work vector c holds A*u of the
+ * last u on return.  Every rank enqueues the same number, so RCCL calls match.  Both modes of pa_cg_solve_all: every part of
+ * one process, or one part per process over RCCL.  The u update always runs
+ * as its own sweep (pa_tune "cg_fuse" does not apply).  It fails with a
+ * message, before anything is touched, on a null argument or handle,
+ * batch < 1, a complex element type, vectors of another size, element type
+ * or context, and owned lids that are not contiguous.
+ * history (optional, maxiter doubles): the residual after each iteration. */
+int pa_pcg_solve_all(int n, pa_mat* const A[], pa_vec* const x[], const pa_vec* const b[],
+                     const pa_vec* const d[], pa_vec* const u[], pa_vec* const r[], pa_vec* const c[],
+                     const pa_index* const idx[], pa_xchg* const xg[], double reltol, double abstol,
+                     int64_t maxiter, int batch, int64_t* iterations, double* residual, double* history);
+
 /* The u-update variant choice of pa_cg_solve_all's auto mode (pa_tune
  * "cg_fuse" 2): the first timed batch runs the sweep, the second the fused
  * update; with one part per process (RCCL) every rank reduces the two

@@ -1494,24 +1494,48 @@ function pcg_update!(x::HIPVector{T}, r::HIPVector{T}, u::HIPVector{T}, c::HIPVe
   res[], rho[]
 end
 
+# every part's owned lids are 1..num_oids (the layout the fused reductions ride on)
+_own_contig(r::PRange) =
+  all(s -> collect(s.oid_to_lid) == collect(1:length(s.oid_to_lid)), r.partition.parts)
+
 # ---- IterativeSolvers.cg! (v0.9) with the recurrence on the device --------
 # (pa_cg_solve_all: the same iterates as the generic cg! over the
 # specialisations above, bit for bit, with no host round trip per iteration)
 # log = true returns IterativeSolvers' ConvergenceHistory: that keeps the
 # generic cg! (over the specialisations above); verbose is not printed here.
-# Pl = HIPJacobi(A) keeps the generic cg! too: its ldiv!(c, Pl, r), dot, mul!
-# and broadcasts are the device operations above.
+# Pl = HIPJacobi(A) with a real T, no log, no statevars and a range whose
+# owned lids are contiguous runs the
+# preconditioned recurrence on the device as well (pa_pcg_solve_all: the
+# iterates of the generic cg! over ldiv!(c, Pl, r), dot, mul! and the
+# broadcasts above, with ρ, β, α of type T).  Any other Pl keeps the generic
+# cg!, whose operations on HIP vectors are still the device ones.
 function IterativeSolvers.cg!(x::HIPVector{T}, A::HIPMatrix{T}, b::HIPVector{T};
                               abstol::Real=zero(real(T)), reltol::Real=sqrt(eps(real(T))),
                               maxiter::Int=size(A, 2), log::Bool=false, initially_zero::Bool=false,
                               kwargs...) where {T<:DeviceEltype}
-  if log || haskey(kwargs, :Pl) || haskey(kwargs, :statevars)
+  Pl = get(kwargs, :Pl, nothing)
+  # pa_pcg_solve_all needs owned lids 1..num_oids on every part; other ranges
+  # (with_ghost, periodic) keep the generic iterate, as before
+  jacobi = Pl isa HIPJacobi && T <: PcgEltype && length(kwargs) == 1 && _own_contig(x.rows)
+  if log || haskey(kwargs, :statevars) || !(Pl === nothing || jacobi)
     return invoke(IterativeSolvers.cg!, Tuple{Any,Any,Any}, x, A, b; abstol=abstol, reltol=reltol,
                   maxiter=maxiter, log=log, initially_zero=initially_zero, kwargs...)
   end
   u, r, c = similar(x), similar(x), similar(x)
   bb = b.rows === x.rows ? b : copyto!(similar(x), b)
   its = Ref{Int64}(0); res = Ref{Float64}(0.0)
+  if jacobi
+    d = Pl.d.rows === x.rows ? Pl.d : PartitionedArrays.exchange!(copyto!(similar(x), Pl.d))
+    check(ccall((:pa_pcg_solve_all, libpa), Cint,
+                (Cint, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}},
+                 Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}},
+                 Float64, Float64, Int64, Cint, Ref{Int64}, Ref{Float64}, Ptr{Float64}),
+                num_parts(x.values), dev_mat(A), dev_vec(x), dev_vec(bb), dev_vec(d), dev_vec_nocopy(u),
+                dev_vec_nocopy(r), dev_vec_nocopy(c), dev_idx(x.rows), dev_xchg(x.rows),
+                Float64(reltol), Float64(abstol), maxiter, Cint(16), its, res, Ptr{Float64}(C_NULL)))
+    mark_device_newer!(x)
+    return x
+  end
   check(ccall((:pa_cg_solve_all, libpa), Cint,
               (Cint, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}},
                Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}},

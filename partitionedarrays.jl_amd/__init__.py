@@ -26,7 +26,7 @@ from .pvector import (Broadcasted, ExprProgram, abs2, all_, any_, assign_, conj,
 from .pvector import async_assemble_, async_exchange_, record, wait_all  # noqa: F401
 from .pvector import MatrixView, VectorView, add_coo_, global_view, local_view  # noqa: F401
 from .pvector import PLU, findnz, gather, ldiv_, lu, lu_, scatter_, solve, zerox  # noqa: F401
-from .pvector import Jacobi, diag, pcg_apply_, pcg_update_  # noqa: F401
+from .pvector import Jacobi, cg_device_, diag, pcg_apply_, pcg_update_  # noqa: F401
 from .device import DeviceArray, DeviceTable  # noqa: F401
 from .pvector import async_exchange_table_, exchange_table_  # noqa: F401
 from .ptimers import PTimer  # noqa: F401

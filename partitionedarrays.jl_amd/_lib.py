@@ -140,6 +140,9 @@ _SIGS = {
     "pa_cg_solve_all": [C.c_int, C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.POINTER(_p),
                         C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.c_double, C.c_double, C.c_int64, C.c_int,
                         _i64p, C.POINTER(C.c_double), C.POINTER(C.c_double)],
+    "pa_pcg_solve_all": [C.c_int, C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.POINTER(_p),
+                         C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.c_double, C.c_double, C.c_int64,
+                         C.c_int, _i64p, C.POINTER(C.c_double), C.POINTER(C.c_double)],
     "pa_exchange_all": [C.c_int, C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.c_int, C.c_int, C.c_int],
     "pa_exchange_all_async": [C.c_int, C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.c_int, C.c_int, C.c_int,
                               C.POINTER(_p), C.POINTER(_p)],

@@ -159,7 +159,10 @@ void launch_mat_diag(const pa_mat* A, const int32_t* own, void* d, int64_t nd, h
 void launch_pcg_apply(int dtype, int64_t n, int64_t noids, void* c, const void* r, const void* d, double* part,
                       int nb, hipStream_t st);
 void launch_pcg_update(int dtype, int64_t n, int64_t noids, void* x, void* r, const void* u, void* c, const void* d,
-                       const void* alpha, void* part, int nb, hipStream_t st);
+                       const void* alpha, const PCGState* cst, void* part, int nb, hipStream_t st);
+void launch_pcg_xu(int dtype, int64_t n, void* u, const void* c, const PCGState* cst, hipStream_t st);
+void launch_pcg_alpha(int dtype, int P, const void* gathered, PCGState* cst, hipStream_t st);
+void launch_pcg_step(int dtype, int P, const void* gathered, PCGState* cst, double* history, hipStream_t st);
 
 }  // namespace pa
 
@@ -4822,8 +4825,8 @@ int pa_pcg_update_all(int n, pa_vec* const x[], pa_vec* const r[], const pa_vec*
     HIPC(hipSetDevice(cx->device));
     const int64_t m = x[i]->n;
     const int nb = pcg_blocks(m);
-    launch_pcg_update(dt, m, idx[i]->noids, x[i]->d, r[i]->d, u[i]->d, c[i]->d, d[i]->d, alpha, cx->d_partials, nb,
-                      cx->s_main);
+    launch_pcg_update(dt, m, idx[i]->noids, x[i]->d, r[i]->d, u[i]->d, c[i]->d, d[i]->d, alpha, nullptr,
+                      cx->d_partials, nb, cx->s_main);
     // {Σ r², Σ c*r} per part: one c128 accumulator, folded componentwise
     launch_fold(1, nb, cx->d_partials, cx->d_fold, cx->d_result, cx->d_ticket, cx->s_main);
   }
@@ -4850,6 +4853,7 @@ struct CGRun {
   bool remote = false;
   std::vector<pa_ctx*> ctxs;
   std::vector<CGState*> st;
+  std::vector<PCGState*> pst;       // the preconditioned solve's state (pa_pcg_solve_all) instead of st
   std::vector<double*> hist;
   std::vector<void**> ptrs;         // local mode: per part, device table of the parts' d_result
   void** dsts = nullptr;            // local mode: the local parts' d_gather (device table on part 1's device)
@@ -4859,6 +4863,7 @@ struct CGRun {
     for (int i = 0; i < n; ++i) {
       if (i < (int)ctxs.size()) (void)hipSetDevice(ctxs[i]->device);
       if (i < (int)st.size()) dev_free(st[i]);
+      if (i < (int)pst.size()) dev_free(pst[i]);
       if (i < (int)hist.size()) dev_free(hist[i]);
       if (i < (int)ptrs.size()) dev_free(ptrs[i]);
       if (i < (int)ev_red.size() && ev_red[i]) (void)hipEventDestroy(ev_red[i]);
@@ -4900,6 +4905,48 @@ int cg_gather(CGRun& R, size_t accsz) {
   for (int i = 1; i < R.n; ++i) {
     HIPC(hipSetDevice(R.ctxs[i]->device));
     HIPC(hipStreamWaitEvent(R.ctxs[i]->s_main, R.ev_gat[0], 0));
+  }
+  return 0;
+}
+
+// What a device-driven solve allocates besides its state (R.n, R.P, R.remote
+// and R.ctxs set): the history of every part and, in local mode, the tables,
+// events and peer access of cg_gather.
+int cg_run_setup(CGRun& R, bool history, int64_t maxiter) {
+  const int n = R.n;
+  std::vector<int> part_pos(R.P + 1, -1);
+  for (int i = 0; i < n; ++i) part_pos[R.ctxs[i]->part] = i;
+  R.hist.assign(n, nullptr);
+  R.ptrs.assign(n, nullptr);
+  R.ev_red.assign(n, nullptr);
+  R.ev_gat.assign(n, nullptr);
+  for (int i = 0; i < n; ++i) {
+    pa_ctx* cx = R.ctxs[i];
+    HIPC(hipSetDevice(cx->device));
+    if (history && maxiter > 0) HIPC(hipMalloc((void**)&R.hist[i], (size_t)maxiter * sizeof(double)));
+    if (!R.remote) {
+      std::vector<void*> tab(R.P, nullptr);
+      for (int p = 1; p <= R.P; ++p) tab[p - 1] = R.ctxs[part_pos[p]]->d_result;
+      if (dev_upload(&R.ptrs[i], tab)) return -1;
+      HIPC(hipEventCreateWithFlags(&R.ev_red[i], hipEventDisableTiming));
+      HIPC(hipEventCreateWithFlags(&R.ev_gat[i], hipEventDisableTiming));
+      for (int j = 0; j < n; ++j) {  // the gather kernel reads the other devices' results
+        const int dj = R.ctxs[j]->device;
+        if (dj == cx->device) continue;
+        int ok = 0;
+        HIPC(hipDeviceCanAccessPeer(&ok, cx->device, dj));
+        CHECK_ARG(ok, "cg!: the device CG over parts on several devices of one process needs peer access");
+        hipError_t e = hipDeviceEnablePeerAccess(dj, 0);
+        if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) HIPC(e);
+        (void)hipGetLastError();
+      }
+    }
+  }
+  if (!R.remote) {  // the destinations of the one-kernel all-gather (local parts in position order)
+    std::vector<void*> d(n);
+    for (int i = 0; i < n; ++i) d[i] = R.ctxs[i]->d_gather;
+    HIPC(hipSetDevice(R.ctxs[0]->device));
+    if (dev_upload(&R.dsts, d)) return -1;
   }
   return 0;
 }
@@ -4961,42 +5008,12 @@ int pa_cg_solve_all(int n, pa_mat* const A[], pa_vec* const x[], const pa_vec* c
   }
   R.remote = R.ctxs[0]->comm && !R.ctxs[0]->rank_of_part && n == 1;  // one part per process
   CHECK_ARG(R.remote || n == R.P, "cg!: pass every part held by this process, or use one part per process with RCCL");
-  std::vector<int> part_pos(R.P + 1, -1);
-  for (int i = 0; i < n; ++i) part_pos[R.ctxs[i]->part] = i;
   R.st.assign(n, nullptr);
-  R.hist.assign(n, nullptr);
-  R.ptrs.assign(n, nullptr);
-  R.ev_red.assign(n, nullptr);
-  R.ev_gat.assign(n, nullptr);
   for (int i = 0; i < n; ++i) {
-    pa_ctx* cx = R.ctxs[i];
-    HIPC(hipSetDevice(cx->device));
+    HIPC(hipSetDevice(R.ctxs[i]->device));
     HIPC(hipMalloc((void**)&R.st[i], sizeof(CGState)));
-    if (history && maxiter > 0) HIPC(hipMalloc((void**)&R.hist[i], (size_t)maxiter * sizeof(double)));
-    if (!R.remote) {
-      std::vector<void*> tab(R.P, nullptr);
-      for (int p = 1; p <= R.P; ++p) tab[p - 1] = R.ctxs[part_pos[p]]->d_result;
-      if (dev_upload(&R.ptrs[i], tab)) return -1;
-      HIPC(hipEventCreateWithFlags(&R.ev_red[i], hipEventDisableTiming));
-      HIPC(hipEventCreateWithFlags(&R.ev_gat[i], hipEventDisableTiming));
-      for (int j = 0; j < n; ++j) {  // the gather kernel reads the other devices' results
-        const int dj = R.ctxs[j]->device;
-        if (dj == cx->device) continue;
-        int ok = 0;
-        HIPC(hipDeviceCanAccessPeer(&ok, cx->device, dj));
-        CHECK_ARG(ok, "cg!: the device CG over parts on several devices of one process needs peer access");
-        hipError_t e = hipDeviceEnablePeerAccess(dj, 0);
-        if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) HIPC(e);
-        (void)hipGetLastError();
-      }
-    }
   }
-  if (!R.remote) {  // the destinations of the one-kernel all-gather (local parts in position order)
-    std::vector<void*> d(n);
-    for (int i = 0; i < n; ++i) d[i] = R.ctxs[i]->d_gather;
-    HIPC(hipSetDevice(R.ctxs[0]->device));
-    if (dev_upload(&R.dsts, d)) return -1;
-  }
+  if (cg_run_setup(R, history != nullptr, maxiter)) return -1;
   // setup (cg_iterator!): u = 0; r = b; c = A*x; r .-= c; residual = norm(r);
   // tolerance = max(reltol*norm(b), abstol)
   unsigned char one[16], zero[16];
@@ -5193,6 +5210,150 @@ int pa_cg_solve_all(int n, pa_mat* const A[], pa_vec* const x[], const pa_vec* c
       HIPC(hipSetDevice(R.ctxs[i]->device));
       HIPC(hipStreamSynchronize(R.ctxs[i]->s_main));
     }
+  }
+  *iterations = h.it;
+  *residual = h.res;
+  if (history && h.it > 0) {
+    HIPC(hipSetDevice(R.ctxs[0]->device));
+    HIPC(hipMemcpy(history, R.hist[0], (size_t)h.it * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Device-driven Jacobi-preconditioned CG (kernels in
+// pa_pcg.hip): pa_cg_solve_all's scheme — the state on the device (PCGState
+// per part), `batch` iterations enqueued between reads of the done flag, each
+// reduction ending in cg_gather and a fold in part order on every part — over
+// the preconditioned iterate, whose scalars are of the element type.  The u
+// update always runs as its own sweep (pa_tune cg_fuse does not apply).
+// After the solve is done the rest of its batch (at most batch-1 iterations)
+// still runs the SpMV, the folds and the gathers: spmv_impl takes no PCGState,
+// so c — a work vector — holds A*u of the final u afterwards, and that work is
+// wasted; x, r, u and the state are not touched (their kernels return).
+int pa_pcg_solve_all(int n, pa_mat* const A[], pa_vec* const x[], const pa_vec* const b[],
+                     const pa_vec* const d[], pa_vec* const u[], pa_vec* const r[], pa_vec* const c[],
+                     const pa_index* const idx[], pa_xchg* const xg[], double reltol, double abstol,
+                     int64_t maxiter, int batch, int64_t* iterations, double* residual, double* history) {
+  const std::string w = "pa_pcg_solve_all: ";
+  CHECK_ARG(n >= 1 && A && x && b && d && u && r && c && idx && iterations && residual, w + "null argument");
+  CHECK_ARG(batch >= 1, w + "batch must be >= 1");
+  for (int i = 0; i < n; ++i)
+    CHECK_ARG(A[i] && x[i] && b[i] && d[i] && u[i] && r[i] && c[i] && idx[i], w + "null handle");
+  const int dt = A[0]->dtype;
+  CHECK_ARG(real_dtype(dt), w + "complex element types are not supported (Float32 and Float64 only)");
+  TuneScope ts(A[0]->ctx);
+  CGRun R;
+  R.n = n;
+  R.P = A[0]->ctx->nparts;
+  for (int i = 0; i < n; ++i) {
+    const int64_t m = x[i]->n;
+    CHECK_ARG(A[i]->dtype == dt, w + "element types differ");
+    for (const pa_vec* v : {(const pa_vec*)x[i], b[i], d[i], (const pa_vec*)u[i], (const pa_vec*)r[i],
+                            (const pa_vec*)c[i]}) {
+      CHECK_ARG(v->dtype == dt, w + "element types differ");
+      CHECK_ARG(v->n == m && v->ctx == A[i]->ctx,
+                w + "x, b, d and the work vectors must share a.cols' partition and the matrix's context");
+    }
+    CHECK_ARG(idx[i]->nlids == m, w + "the index set does not describe the vectors");
+    CHECK_ARG(idx[i]->own_contig, w + "the owned lids must be contiguous (0..noids-1)");
+    CHECK_ARG(A[i]->ctx->nparts == R.P, w + "parts of different partitions");
+    R.ctxs.push_back(A[i]->ctx);
+  }
+  R.remote = R.ctxs[0]->comm && !R.ctxs[0]->rank_of_part && n == 1;  // one part per process
+  CHECK_ARG(R.remote || n == R.P, w + "pass every part held by this process, or use one part per process with RCCL");
+  R.pst.assign(n, nullptr);
+  for (int i = 0; i < n; ++i) {
+    HIPC(hipSetDevice(R.ctxs[i]->device));
+    HIPC(hipMalloc((void**)&R.pst[i], sizeof(PCGState)));
+  }
+  if (cg_run_setup(R, history != nullptr, maxiter)) return -1;
+  // setup (cg_iterator! with Pl): u = 0; r = b; c = A*x; r .-= c; residual =
+  // norm(r); tolerance = max(reltol*norm(b), abstol); ρ = one(T)
+  unsigned char one[16], zero[16];
+  scalar_one(dt, one, 1.0);
+  scalar_one(dt, zero, 0.0);
+  for (int i = 0; i < n; ++i) {
+    HIPC(hipSetDevice(R.ctxs[i]->device));
+    launch_fill(dt, u[i]->n, 0, nullptr, u[i]->d, zero, R.ctxs[i]->s_main);
+    launch_copy(dt, r[i]->n, nullptr, r[i]->d, nullptr, b[i]->d, R.ctxs[i]->s_main);
+  }
+  HIPC(hipGetLastError());
+  if (spmv_impl(n, A, c, idx, x, idx, xg, one, zero, false)) return -1;
+  for (int i = 0; i < n; ++i) {
+    HIPC(hipSetDevice(R.ctxs[i]->device));
+    launch_axpby(dt, r[i]->n, nullptr, r[i]->d, c[i]->d, zero, 3, R.ctxs[i]->s_main);
+  }
+  double res0 = 0.0, nb = 0.0;
+  if (pa_norm2_all(n, (const pa_vec* const*)r, idx, &res0)) return -1;
+  if (pa_norm2_all(n, b, idx, &nb)) return -1;
+  PCGState h{};
+  h.res = res0;
+  h.tol = std::max(reltol * nb, abstol);
+  h.it = 0;
+  h.maxiter = maxiter;
+  h.done = (0 >= maxiter || res0 <= h.tol) ? 1 : 0;
+  h.rho = 1.0;
+  h.rho_prev = 1.0;
+  h.alpha = 0.0;
+  if (!h.done) {  // the first c = Pl \ r and ρ = dot(c, r); every later one rides in the update
+    unsigned char rho[16] = {0};
+    if (pa_pcg_apply_all(n, c, (const pa_vec* const*)r, d, idx, rho)) return -1;
+    h.rho = dt == PA_F32 ? (double)*(const float*)rho : *(const double*)rho;
+  }
+  for (int i = 0; i < n; ++i) {
+    HIPC(hipSetDevice(R.ctxs[i]->device));
+    HIPC(hipMemcpyAsync(R.pst[i], &h, sizeof(PCGState), hipMemcpyHostToDevice, R.ctxs[i]->s_main));
+    HIPC(hipStreamSynchronize(R.ctxs[i]->s_main));
+  }
+  // one part in this process and no other process: the scalar kernels read
+  // the part's d_result (no gather, no events)
+  const bool tail = !R.remote && R.P == 1;
+  int64_t enqueued = 0;
+  bool done = h.done != 0;
+  while (!done && enqueued < maxiter) {
+    const int64_t k = std::min<int64_t>(batch, maxiter - enqueued);  // the same on every rank
+    for (int64_t t = 0; t < k; ++t) {
+      for (int i = 0; i < n; ++i) {  // u .= c .+ β.*u, β = ρ/ρ_prev
+        HIPC(hipSetDevice(R.ctxs[i]->device));
+        launch_pcg_xu(dt, u[i]->n, u[i]->d, c[i]->d, R.pst[i], R.ctxs[i]->s_main);
+      }
+      // mul!(c, A, u) with dot(u, c) accumulated by the SpMV; α = ρ / dot(u, c)
+      if (spmv_impl(n, A, c, idx, u, idx, xg, one, zero, true)) return -1;
+      if (!tail && cg_gather(R, 8)) return -1;
+      for (int i = 0; i < n; ++i) {
+        pa_ctx* cx = R.ctxs[i];
+        HIPC(hipSetDevice(cx->device));
+        launch_pcg_alpha(dt, R.P, tail ? cx->d_result : cx->d_gather, R.pst[i], cx->s_main);
+      }
+      for (int i = 0; i < n; ++i) {  // x .+= α.*u; r .-= α.*c; c = Pl \ r; {Σr², Σc·r}
+        pa_ctx* cx = R.ctxs[i];
+        HIPC(hipSetDevice(cx->device));
+        const int64_t m = x[i]->n;
+        const int nbk = pcg_blocks(m);
+        launch_pcg_update(dt, m, idx[i]->noids, x[i]->d, r[i]->d, u[i]->d, c[i]->d, d[i]->d, nullptr, R.pst[i],
+                          cx->d_partials, nbk, cx->s_main);
+        launch_fold(1, nbk, cx->d_partials, cx->d_fold, cx->d_result, cx->d_ticket, cx->s_main);
+      }
+      if (!tail && cg_gather(R, 16)) return -1;
+      for (int i = 0; i < n; ++i) {  // residual = norm(r); ρ_prev = ρ; ρ = dot(c, r); it += 1; done?
+        pa_ctx* cx = R.ctxs[i];
+        HIPC(hipSetDevice(cx->device));
+        launch_pcg_step(dt, R.P, tail ? cx->d_result : cx->d_gather, R.pst[i], R.hist[i], cx->s_main);
+      }
+      HIPC(hipGetLastError());
+    }
+    enqueued += k;
+    // every part holds the same state; read the first's
+    pa_ctx* c0 = R.ctxs[0];
+    HIPC(hipSetDevice(c0->device));
+    HIPC(hipMemcpyAsync(c0->h_pinned, R.pst[0], sizeof(PCGState), hipMemcpyDeviceToHost, c0->s_main));
+    for (int i = 0; i < n; ++i) {
+      HIPC(hipSetDevice(R.ctxs[i]->device));
+      HIPC(hipStreamSynchronize(R.ctxs[i]->s_main));
+    }
+    std::memcpy(&h, c0->h_pinned, sizeof(PCGState));
+    done = h.done != 0;
   }
   *iterations = h.it;
   *residual = h.res;

@@ -224,6 +224,23 @@ struct CGState {
   int64_t xit;       // iterations whose x .+= α.*u is applied (deferred into the next u update)
 };
 
+// Device-resident scalars of the device-driven Jacobi-preconditioned CG
+// (pa_pcg_solve_all), one copy per part as above.  Unlike
+// CGState's, the recurrence's scalars are of the element type T: rho,
+// rho_prev and alpha hold T values (a Float32 widened exactly) and the
+// kernels convert them back before every operation, which then runs in T.
+struct PCGState {
+  double res;        // norm(r), Float64
+  double tol;        // max(reltol*norm(b), abstol)
+  int64_t it;        // iterations done
+  int64_t maxiter;
+  int32_t done;      // it >= maxiter || res <= tol
+  int32_t pad;
+  double rho;        // ρ = dot(Pl \ r, r) of the current r
+  double rho_prev;   // the ρ of the iteration before (one(T) before the first)
+  double alpha;      // α = ρ / dot(u, A*u)
+};
+
 // Grouped launches (parts of one process sharing a stream pair): one launch
 // per phase covers up to PA_GROUP_MAX parts (kernel-argument tables).
 constexpr int PA_GROUP_MAX = 8;

@@ -1,7 +1,8 @@
 // pa_pcg.hip — Jacobi-preconditioned CG (pa_mat_diag, pa_pcg_apply_all,
-// pa_pcg_update_all): diag(A) read off the SELL layout, the
-// preconditioner's apply fused with ρ = dot(c, r), and the tail of one
-// iteration fused with the head of the next.
+// pa_pcg_update_all, pa_pcg_solve_all): diag(A) read off the
+// SELL layout, the preconditioner's apply fused with ρ = dot(c, r), the tail
+// of one iteration fused with the head of the next, and the kernels of the
+// device-driven recurrence (its scalars in a PCGState).
 //
 // Float32 and Float64 only.  Every element is evaluated in T, rounded at
 // every operation (the library is compiled with -ffp-contract=off; `/` is
@@ -140,10 +141,17 @@ void pcg_apply_t(int64_t n, int64_t noids, void* c, const void* r, const void* d
 // preconditioned new residual on exit, read and written at the same index by
 // the same lane.  The owned Σ r_i² (.re) and Σ c_i*r_i (.im) of the new
 // values as one c128 partial per block (contiguous owned lids 0..noids-1).
-template <typename T, int V>
+// DEV: α comes from the device PCG state (pa_pcg_solve_all) and a finished
+// solve is a no-op.
+template <typename T, int V, bool DEV>
 __global__ __launch_bounds__(256) void k_pcg_update(int64_t n, int64_t noids, T* __restrict__ x, T* __restrict__ r,
                                                     const T* __restrict__ u, T* __restrict__ c,
-                                                    const T* __restrict__ d, T alpha, c128* __restrict__ part) {
+                                                    const T* __restrict__ d, T alpha,
+                                                    const PCGState* __restrict__ st, c128* __restrict__ part) {
+  if (DEV) {
+    if (st->done) return;
+    alpha = (T)st->alpha;
+  }
   using P = Pack<T, V>;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -180,16 +188,92 @@ __global__ __launch_bounds__(256) void k_pcg_update(int64_t n, int64_t noids, T*
 
 template <typename T>
 void pcg_update_t(int64_t n, int64_t noids, void* x, void* r, const void* u, void* c, const void* d,
-                  const void* alpha, c128* part, int nb, hipStream_t st) {
+                  const void* alpha, const PCGState* cst, c128* part, int nb, hipStream_t st) {
   constexpr int V = 16 / sizeof(T);
   const bool aligned = ((uintptr_t)x | (uintptr_t)r | (uintptr_t)u | (uintptr_t)c | (uintptr_t)d) % 16 == 0;
-  const T a = *(const T*)alpha;
-  if (aligned)
-    hipLaunchKernelGGL((k_pcg_update<T, V>), dim3(nb), dim3(256), 0, st, n, noids, (T*)x, (T*)r, (const T*)u, (T*)c,
-                       (const T*)d, a, part);
-  else
-    hipLaunchKernelGGL((k_pcg_update<T, 1>), dim3(nb), dim3(256), 0, st, n, noids, (T*)x, (T*)r, (const T*)u, (T*)c,
-                       (const T*)d, a, part);
+  const T a = alpha ? *(const T*)alpha : T(0);
+#define PA_PU(VV, DD)                                                                                           \
+  hipLaunchKernelGGL((k_pcg_update<T, VV, DD>), dim3(nb), dim3(256), 0, st, n, noids, (T*)x, (T*)r, (const T*)u, \
+                     (T*)c, (const T*)d, a, cst, part)
+  if (cst) {
+    if (aligned) PA_PU(V, true); else PA_PU(1, true);
+  } else {
+    if (aligned) PA_PU(V, false); else PA_PU(1, false);
+  }
+#undef PA_PU
+}
+
+// ---- the device-driven recurrence (pa_pcg_solve_all) -----------------------
+// The same arithmetic as the host-driven fused loop (pvector._pcg over
+// pa_vec_axpby, pa_spmv_dot_all and pa_pcg_update_all), the scalars on one
+// thread, so the device recurrence equals it bit for bit.
+
+// u .= c .+ β.*u over all lids, β = ρ/ρ_prev: one division in T, then per
+// element the product and the sum each rounded in T (pa_vec_axpby mode 0 with
+// a scalar of the element type).  A finished solve is a no-op.
+template <typename T, int V>
+__global__ __launch_bounds__(256) void k_pcg_xu(int64_t n, T* __restrict__ u, const T* __restrict__ c,
+                                                const PCGState* __restrict__ st) {
+  if (st->done) return;
+  const T b = (T)st->rho / (T)st->rho_prev;
+  using P = Pack<T, V>;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const int64_t nv = n / V;
+  for (int64_t j = t; j < nv; j += stride) {
+    P uv = reinterpret_cast<const P*>(u)[j];
+    const P cv = reinterpret_cast<const P*>(c)[j];
+#pragma unroll
+    for (int e = 0; e < V; ++e) uv.v[e] = cv.v[e] + b * uv.v[e];
+    reinterpret_cast<P*>(u)[j] = uv;
+  }
+  for (int64_t i = nv * V + t; i < n; i += stride) u[i] = c[i] + b * u[i];
+}
+
+template <typename T>
+void pcg_xu_t(int64_t n, void* u, const void* c, const PCGState* cst, hipStream_t st) {
+  constexpr int V = 16 / sizeof(T);
+  const bool aligned = ((uintptr_t)u | (uintptr_t)c) % 16 == 0;
+  const int64_t nw = aligned ? (n + V - 1) / V : n;
+  const int nb = (int)std::min<int64_t>(8192, std::max<int64_t>(1, (nw + 255) / 256));
+  if (aligned) hipLaunchKernelGGL((k_pcg_xu<T, V>), dim3(nb), dim3(256), 0, st, n, (T*)u, (const T*)c, cst);
+  else hipLaunchKernelGGL((k_pcg_xu<T, 1>), dim3(nb), dim3(256), 0, st, n, (T*)u, (const T*)c, cst);
+}
+
+// the dot(u, c) values of the P parts (Float64 accumulators, part order) →
+// dot = reduce(+; init=zero(T)) over the part values, each rounded to T
+// (fold_parts, pa_api.cpp) → α = ρ / dot, one division in T
+template <typename T>
+__global__ void k_pcg_alpha(int P, const double* __restrict__ gathered, PCGState* __restrict__ st) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  if (st->done) return;
+  T s = (T)0;
+  for (int p = 0; p < P; ++p) s = s + (T)gathered[p];
+  st->alpha = (double)((T)st->rho / s);
+}
+
+// the {Σr², Σc·r} values of the P parts → both folded as above;
+// residual = sqrt(Σr²) in Float64; ρ_prev = ρ; ρ = Σc·r; it += 1;
+// history[it-1] = residual; done = it >= maxiter || residual <= tol (a NaN
+// residual never satisfies <=: such a solve runs to maxiter, as on the host).
+template <typename T>
+__global__ void k_pcg_step(int P, const c128* __restrict__ gathered, PCGState* __restrict__ st,
+                           double* __restrict__ history) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  if (st->done) return;
+  T rr = (T)0, cr = (T)0;
+  for (int p = 0; p < P; ++p) {
+    rr = rr + (T)gathered[p].re;
+    cr = cr + (T)gathered[p].im;
+  }
+  const double res = sqrt((double)rr);
+  st->res = res;
+  st->rho_prev = st->rho;
+  st->rho = (double)cr;
+  const int64_t it = st->it + 1;
+  st->it = it;
+  if (history) history[it - 1] = res;
+  st->done = (it >= st->maxiter || res <= st->tol) ? 1 : 0;
 }
 
 }  // namespace
@@ -215,12 +299,31 @@ void launch_pcg_apply(int dtype, int64_t n, int64_t noids, void* c, const void* 
   else pcg_apply_t<double>(n, noids, c, r, d, part, nb, st);
 }
 
-// alpha: host scalar of the element type; part[0..nb-1]: the blocks'
-// {Σ r_i², Σ c_i*r_i} over lids < noids
+// alpha: host scalar of the element type (cst null), or read from the device
+// PCG state; part[0..nb-1]: the blocks' {Σ r_i², Σ c_i*r_i} over lids < noids
 void launch_pcg_update(int dtype, int64_t n, int64_t noids, void* x, void* r, const void* u, void* c, const void* d,
-                       const void* alpha, void* part, int nb, hipStream_t st) {
-  if (dtype == PA_F32) pcg_update_t<float>(n, noids, x, r, u, c, d, alpha, (c128*)part, nb, st);
-  else pcg_update_t<double>(n, noids, x, r, u, c, d, alpha, (c128*)part, nb, st);
+                       const void* alpha, const PCGState* cst, void* part, int nb, hipStream_t st) {
+  if (dtype == PA_F32) pcg_update_t<float>(n, noids, x, r, u, c, d, alpha, cst, (c128*)part, nb, st);
+  else pcg_update_t<double>(n, noids, x, r, u, c, d, alpha, cst, (c128*)part, nb, st);
+}
+
+void launch_pcg_xu(int dtype, int64_t n, void* u, const void* c, const PCGState* cst, hipStream_t st) {
+  if (dtype == PA_F32) pcg_xu_t<float>(n, u, c, cst, st);
+  else pcg_xu_t<double>(n, u, c, cst, st);
+}
+
+// gathered: P Float64 values (the parts' dot(u, c))
+void launch_pcg_alpha(int dtype, int P, const void* gathered, PCGState* cst, hipStream_t st) {
+  if (dtype == PA_F32) hipLaunchKernelGGL(k_pcg_alpha<float>, dim3(1), dim3(64), 0, st, P, (const double*)gathered, cst);
+  else hipLaunchKernelGGL(k_pcg_alpha<double>, dim3(1), dim3(64), 0, st, P, (const double*)gathered, cst);
+}
+
+// gathered: P c128 values (the parts' {Σr², Σc·r})
+void launch_pcg_step(int dtype, int P, const void* gathered, PCGState* cst, double* history, hipStream_t st) {
+  if (dtype == PA_F32)
+    hipLaunchKernelGGL(k_pcg_step<float>, dim3(1), dim3(64), 0, st, P, (const c128*)gathered, cst, history);
+  else
+    hipLaunchKernelGGL(k_pcg_step<double>, dim3(1), dim3(64), 0, st, P, (const c128*)gathered, cst, history);
 }
 
 }  // namespace pa

@@ -1440,7 +1440,8 @@ def cg_(x: PVector, A: PSparseMatrix, b: PVector, reltol=None, abstol=0.0, maxit
     the done flag; results equal the host-driven fused loop bit for bit.
 
     Pl: a left preconditioner (Jacobi); the preconditioned iterate then runs
-    (_pcg), host-driven, Float32 / Float64.  Pl=None is the loop above."""
+    (_pcg), host-driven, Float32 / Float64 (cg_device_ runs it with its
+    scalars on the device).  Pl=None is the loop above."""
     real = np.float32 if x.dtype in (np.float32, np.complex64) else np.float64
     if reltol is None:  # sqrt(eps(real(eltype(b)))), in that type
         reltol = float(np.sqrt(np.finfo(real).eps))
@@ -1448,7 +1449,8 @@ def cg_(x: PVector, A: PSparseMatrix, b: PVector, reltol=None, abstol=0.0, maxit
         maxiter = len(A.cols)
     if Pl is not None:
         if device:
-            raise NotImplementedError("cg_(Pl=..., device=True): the preconditioned recurrence is host-driven")
+            raise NotImplementedError("cg_(Pl=..., device=True): cg_ drives the preconditioned recurrence from the "
+                                      "host; cg_device_(x, A, b, Pl=...) runs it with its scalars on the device")
         return _pcg(x, A, b, Pl, reltol, abstol, maxiter, history, fused)
     if device:
         return _cg_device(x, A, b, reltol, abstol, maxiter, history, batch)
@@ -1641,6 +1643,58 @@ def _pcg(x: PVector, A: PSparseMatrix, b: PVector, Pl, reltol, abstol, maxiter, 
             if history is not None:
                 history.append(residual)
     return x
+
+
+def _pcg_device(x: PVector, A: PSparseMatrix, b: PVector, Pl, reltol, abstol, maxiter, history, batch):
+    """_pcg's fused loop with its scalars on the device (pa_pcg_solve_all):
+    the same x, residual history and iteration count, bit for bit."""
+    if not isinstance(Pl, Jacobi):
+        raise TypeError("cg_device_(Pl=...): Pl must be a Jacobi")
+    _real_only(x.dtype, "cg_device_(Pl=...)")
+    if Pl.d.dtype != x.dtype:
+        raise TypeError("cg_device_(Pl=...): the preconditioner's element type differs from x's")
+    if not _own_contig(x):
+        raise ValueError("cg_device_(Pl=...): x needs contiguous owned lids")
+    d = _on_rows(Pl.d, x)
+    if b.rows is not x.rows:  # copyto!(r, b) across partitions copies the owned values
+        bb = x.similar()
+        copyto_(bb, b)
+        b = bb
+    u, r, c = x.similar(), x.similar(), x.similar()
+    ctxs = contexts(A.values)
+    n = len(ctxs)
+    ex = x.rows.exchanger
+    has_x = any(len(ex.parts_rcv.local(p)) or len(ex.parts_snd.local(p)) for p in x.values.part_ids)
+    xg = [device_exchanger(cx, ex, p) for cx, p in zip(ctxs, x.values.part_ids)] if has_x else None
+    its = C.c_int64(0)
+    res = C.c_double(0.0)
+    hist = np.zeros(max(1, int(maxiter)), dtype=np.float64) if history is not None else None
+    _lib.call("pa_pcg_solve_all", n, _hs(A.values.parts), _hs(x.values.parts), _hs(b.values.parts),
+              _hs(d.values.parts), _hs(u.values.parts), _hs(r.values.parts), _hs(c.values.parts),
+              _lib.ptr_array(_idx(x)), _hs(xg) if xg else None, float(reltol), float(abstol), int(maxiter),
+              int(batch), C.byref(its), C.byref(res),
+              hist.ctypes.data_as(C.POINTER(C.c_double)) if hist is not None else None)
+    if history is not None:
+        history.extend(float(v) for v in hist[:its.value])
+    return x
+
+
+def cg_device_(x: PVector, A: PSparseMatrix, b: PVector, Pl=None, reltol=None, abstol=0.0, maxiter=None,
+               history=None, batch=8):
+    """cg_ with the recurrence's scalars on the device: the host enqueues
+    `batch` iterations between reads of the done flag.  Pl=None is
+    cg_(…, device=True) (pa_cg_solve_all); Pl=Jacobi(A) is the preconditioned
+    iterate (pa_pcg_solve_all), Float32 / Float64, whose results equal
+    cg_(…, Pl=Pl, fused=True) bit for bit.  Both need contiguous owned lids
+    (ValueError otherwise)."""
+    real = np.float32 if x.dtype in (np.float32, np.complex64) else np.float64
+    if reltol is None:  # sqrt(eps(real(eltype(b)))), in that type
+        reltol = float(np.sqrt(np.finfo(real).eps))
+    if maxiter is None:
+        maxiter = len(A.cols)
+    if Pl is None:
+        return _cg_device(x, A, b, reltol, abstol, maxiter, history, batch)
+    return _pcg_device(x, A, b, Pl, reltol, abstol, maxiter, history, batch)
 
 
 # ---------------------------------------------------------------------------
